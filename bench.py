@@ -106,6 +106,27 @@ def _baseline_metric() -> str:
         return "UNet denoise steps/sec @ SDXL 1024\u00b2, 50 ref views, 1/2/4/8 MI355X"
 
 
+DUMP_LIMIT_BYTES = 60 * 10**6  # --dump-outputs: array data of all files together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path: str, arrays, limit: int = DUMP_LIMIT_BYTES, seed: int = 0):
+    """--dump-outputs: every tensor of `arrays` (name -> tensor) as `path/<name>.npy`, float32.  When the set is larger than `limit` bytes,
+    each array is cut to the same fraction of its flattened elements, at positions drawn from a generator seeded by `seed` and sorted:
+    the same shapes give the same positions on every run, so two builds stay comparable element for element.  Returns name -> shape written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if total > limit:
+            keep = max(1, a.size * limit // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = list(a.shape)
+    return written
+
+
 def self_launch_argv(n: int, argv, port: int = 0):
     """argv of the N-rank launch of this same command: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
     127.0.0.1 --master-port P bench.py <the caller's arguments>` (the form the driver uses for N > 1).  port = 0 picks a free one."""
@@ -131,6 +152,9 @@ def main():
     ap.add_argument("--poses-per-replay", type=int, default=1, help="target poses batched into ONE denoise step (CFG batch 3 x this): what a rank "
                     "with several poses to sample gains from batching them (the 1280-level GEMMs then run 256-row tiles).  A separate line -- "
                     "`config.poses_per_replay`, metric suffixed -- never the headline; --poses must be a multiple of it per GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path returned from its last step -- "
+                    "the final latents of every pose of the job, [poses, 4, latent, latent] -- as DIR/latents.npy (float32, at most 64 MB in "
+                    "all).  The inputs depend on the arguments alone, so two builds run with the same arguments compare output for output")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip per-kernel HIP-event timing")
     ap.add_argument("--no-graph", action="store_true", help="launch every step eagerly instead of replaying the steady-state step from a hipGraph")
@@ -149,6 +173,8 @@ def main():
     ap.add_argument("--fp8-attn", action="store_true", help="BASELINE configs[4]: the text / pose-token cross-attention of every block with q K^T and P V on "
                     "fp8 MFMA (cd360_qproj_attn_fp8_bf16) for the whole run; adds an `fp8_tolerance` object (rendered features and eps against the bf16 run)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1: it is the number of timed steps")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: become the launcher.  The same command line is re-run as N ranks (one per GPU) under
@@ -266,15 +292,19 @@ def main():
 
     tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     rank_ms = [elapsed / steps_done * 1e3]
+    latents = torch.cat(finals, 0)  # what the timed path returns: the latent of every pose of this rank after its last step
     if world > 1:
         every = [torch.zeros_like(tmax) for _ in range(world)]
         dist.all_gather(every, tmax)  # per-rank elapsed: the line shows the spread, `value` uses the slowest rank
         rank_ms = [float(t.item()) / steps_done * 1e3 for t in every]
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        gathered = shard.gather_latents(torch.cat(finals, 0), n_poses)  # the job's one exchange: final latents of every pose
+        gathered = shard.gather_latents(latents, n_poses)  # the job's one exchange: final latents of every pose
         assert gathered.shape[0] == n_poses and torch.isfinite(gathered).all()
+        latents = gathered
     elapsed = float(tmax.item())
     assert all(torch.isfinite(f).all() for f in finals)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latents": latents})
 
     sum_steps = args.steps * n_poses  # pose-steps of the whole job
     if rank == 0:

@@ -9,7 +9,7 @@ So the assignment is checked against a fingerprint of the function's SOURCE, tak
 
 and compared with the values below, which tests/golden/make_golden.py computes from /root/reference/sample.py with the same walk (a hash is
 data about the reference, not its text; tests/golden/sample_py_fingerprints.json is the recorded copy, tests/test_host_cpu.py holds the two
-equal and -- where the reference tree is present -- recomputes them from sample.py).  A function with no retrievable source, or whose
+equal and checks the walk's properties on the suite's stand-ins).  A function with no retrievable source, or whose
 fingerprint is not listed, is NOT recognised: it is installed like any other instance-level forward and takes the strict module route,
 with one warning.  `trust(kind, fn)` lets a caller declare one more function as sample.py's sampling mode (a vendored copy with cosmetic
 edits; the stand-ins of tests/golden/sample_py_stub.py)."""

@@ -17,6 +17,8 @@ import json
 import os
 import sys
 
+os.environ["MKL_CBWR"] = "COMPATIBLE"  # MKL's reproducible code path, as tests/conftest.py sets it for the suite
+
 import numpy as np
 import torch
 
@@ -377,6 +379,10 @@ def case_sampler():
             out["sigmas50"] = smp.discretization(50, device="cpu")
             out["sigmas12"] = smp.discretization(12, device="cpu")
             out["table"] = den.sigmas
+            # the float32 (1 - acp) / acp the reference takes the square root of (discretizer.py get_sigmas): IEEE arithmetic, the same
+            # bits on every host -- unlike that square root, which torch runs on MKL's vector math
+            acp = smp.discretization.alphas_cumprod
+            out["ratio"] = torch.tensor((1 - acp) / acp, dtype=torch.float32)
             xin, sin, cin = smp.guider.prepare_inputs(x, torch.full((b,), 3.3), c, uc)
             out["prep_ctx"], out["prep_vec"] = cin["crossattn"], cin["vector"]
             d1, _, _, _ = den(dummy_network, xin, sin, cin)

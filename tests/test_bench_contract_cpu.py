@@ -82,3 +82,27 @@ def test_bench_gpus_n_launches_its_own_ranks():
     assert 1024 < port < 65536
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert 'args.gpus > 1 and "WORLD_SIZE" not in os.environ' in src and "os.execv(sys.executable, self_launch_argv(" in src
+
+
+def test_bench_dump_outputs_writes_float32_within_the_size_bound(tmp_path):
+    """--dump-outputs: arrays within the bound are written whole as float32 .npy; a larger set is cut to a seeded sample of each array's
+    flattened elements that fits the bound, at the same positions on every call (two builds compare element for element)."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.DUMP_LIMIT_BYTES <= 64 * 10**6
+    x = torch.randn(2, 4, 8, 8, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
+    assert bench.dump_outputs(str(tmp_path / "whole"), {"latents": x}) == {"latents": [2, 4, 8, 8]}
+    got = np.load(tmp_path / "whole" / "latents.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.float().numpy())
+    big = {"a": torch.arange(3000, dtype=torch.float64), "b": torch.arange(1000, dtype=torch.float32) + 0.5}
+    for d in ("s1", "s2"):
+        shapes = bench.dump_outputs(str(tmp_path / d), big, limit=2000)
+        assert sum(n for (n,) in shapes.values()) * 4 <= 2000 and shapes["a"][0] > shapes["b"][0] > 0
+    for name, t in big.items():
+        s1, s2 = np.load(tmp_path / "s1" / f"{name}.npy"), np.load(tmp_path / "s2" / f"{name}.npy")
+        assert s1.dtype == np.float32 and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0) and np.isin(s1, t.float().numpy()).all()
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert 'add_argument("--dump-outputs"' in src and 'dump_outputs(args.dump_outputs, {"latents": latents})' in src

@@ -161,3 +161,26 @@ def test_bench_gpus_2_starts_its_own_ranks_and_prints_one_line():
     assert line["n_gpus"] == 2 and line["config"]["world_size"] == 2 and line["config"]["poses"] == 4 and line["config"]["poses_per_gpu"] == 2
     assert line["scaling"] == "weak" and line["value"] > 0 and "sanity_run" in line["config"]
     assert set(line["config"]["rank_ms_per_step"]) == {"min", "max"}
+
+
+def test_bench_dump_outputs_repeats_run_for_run(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the final latents the timed path returned (every pose of the job after its last timed step) as
+    DIR/latents.npy, float32; two runs with the same arguments see the same inputs and write the same latents (the forward is bit-stable),
+    and the line's `steps` / `ms_per_step` are those of the K timed steps asked for."""
+    import numpy as np
+    lines = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--poses", "2", "--steps", "3", "--warmup", "1", "--latent", "32",
+               "--refs", "6", "--no-train-step", "--no-cpu-baseline", "--no-profile", "--dump-outputs", str(tmp_path / run)]
+        res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert res.returncode == 0, res.stderr[-3000:]
+        out = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, res.stdout[-2000:]
+        lines.append(json.loads(out[0]))
+    for line in lines:
+        assert line["steps"] == 3 and line["config"]["poses"] == 2 and line["ms_per_step"] > 0
+        assert abs(line["value"] - 1e3 / line["ms_per_step"]) < 1e-2 * line["value"]  # one pose per replay: pose-steps = replays
+    a, b = np.load(tmp_path / "a" / "latents.npy"), np.load(tmp_path / "b" / "latents.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 4, 32, 32) and np.isfinite(a).all() and a.std() > 0
+    assert not np.array_equal(a[0], a[1])  # two target poses, two start latents
+    assert np.allclose(a, b, rtol=0, atol=1e-5 * float(np.abs(a).max())), float(np.abs(a - b).max())

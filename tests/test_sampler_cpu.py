@@ -36,10 +36,23 @@ def build(guider):
 
 
 def test_schedule_and_table_match_reference_bitwise():
+    """Bit for bit what the reference computes ON THIS HOST: the reference's float32 (1 - acp) / acp (stored: IEEE arithmetic, the same
+    bits everywhere), then its `** 0.5`, which torch runs on MKL's vector math -- whose last bit depends on the host CPU.  The stored
+    tables are that square root on the generating host: at most one float32 ulp from this host's."""
     g = load()
     den, smp = build({"target": "sgm.modules.diffusionmodules.guiders.ScheduledCFGImgTextRef", "params": {"scale": 7.5, "scale_im": 3.5}})
-    assert torch.equal(den.sigmas, g["table"])
-    assert torch.equal(smp.discretization(50), g["sigmas50"]) and torch.equal(smp.discretization(12), g["sigmas12"])
+    ratio = g["ratio"]
+    acp = smp.discretization.alphas_cumprod
+    assert torch.equal(torch.tensor((1 - acp) / acp, dtype=torch.float32), ratio)
+
+    def one_ulp(a, b):
+        return bool(((a - b).abs() <= torch.nextafter(b.abs(), torch.full_like(b, float("inf"))) - b.abs()).all())
+
+    assert torch.equal(den.sigmas, ratio ** 0.5) and one_ulp(den.sigmas, g["table"])
+    for n in (50, 12):
+        t = np.linspace(999, 0, n, endpoint=False).astype(int)[::-1].copy()  # discretizer.py:11-14
+        want = torch.cat([torch.flip(ratio[torch.from_numpy(t)] ** 0.5, (0,)), torch.zeros(1)])
+        assert torch.equal(smp.discretization(n), want) and one_ulp(want, g[f"sigmas{n}"])
     idx = den.sigma_to_idx(torch.tensor([0.03, 3.3, 20.0]))
     assert idx.tolist() == [0, int((g["table"] - 3.3).abs().argmin()), 999]
 
