@@ -94,6 +94,9 @@ SIGNATURES = {
     "cd360_set_tuning": (c_int, [_P]),
     "cd360_get_tuning": (c_int, [_P]),
     "cd360_whatif_build": (c_int, []),
+    "cd360_lowrank_add_bf16": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, c_int, c_int, c_float, _P, c_int64, _P]),
+    "cd360_dropout_apply_bf16": (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int, c_float, _P, c_int64, _P]),
+    "cd360_dropout_tick": (c_int, [_P, _P]),
 }
 
 TUNING_FIELDS = ("gemm_cfg", "gemm_group_m", "gemm_movers", "gemm_ksplit", "conv_cfg", "conv_dma", "conv_kgroup", "conv_wide", "conv_wmajor",

@@ -308,6 +308,17 @@ class MasterAdamW:
             p.copy_(m)
 
 
+_ADAPTERS = {}  # id(unet) -> (module epoch, whether any attention module carries add_lora adapters)
+
+
+def _has_adapters(unet: torch.nn.Module) -> bool:
+    from sgm.modules.attention import _module_epoch
+    ent = _ADAPTERS.get(id(unet))
+    if ent is None or ent[0] != _module_epoch[0]:
+        ent = _ADAPTERS[id(unet)] = (_module_epoch[0], any(getattr(m, "add_lora", False) for m in unet.modules()))
+    return ent[1]
+
+
 def train_step(unet: torch.nn.Module, loss_fn, optimizer, *, noised, timesteps, context, y, pose, input_ref, sigmas_ref, target, target_rgb,
                w, mask, opacity, drop_im=None, mask_ref=None, as_tensors: bool = False, **loss_kw):
     """One step of the fine-tuning loop on already-noised inputs (the engine's denoiser / conditioner / data loading stay outside
@@ -316,6 +327,9 @@ def train_step(unet: torch.nn.Module, loss_fn, optimizer, *, noised, timesteps, 
     The logged terms are read back AFTER the optimiser step has been queued (one host synchronisation per step, at its end, instead of
     four between the forward and the backward pass); as_tensors=True leaves them on the device (no synchronisation at all)."""
     optimizer.zero_grad()
+    if _has_adapters(unet):  # new adapter-dropout masks for this step (a captured step advances the offset on every replay)
+        from . import ops
+        ops.dropout_tick(noised.device)
     out, fgs, alphas, rgbs = unet(noised, timesteps=timesteps, context=context, y=y, pose=pose, input_ref=input_ref, sigmas_ref=sigmas_ref,
                                   mask_ref=mask_ref)
     l2, lfg, lbg, lrgb = loss_fn.get_loss(out, fgs, rgbs, target, target_rgb, w, mask, mask_ref, opacity, alphas)

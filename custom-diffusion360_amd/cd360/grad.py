@@ -398,3 +398,54 @@ class ConcatChannelsFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, d):
         return d[:, :ctx.ca], d[:, ctx.ca:]
+
+
+class LoraFn(torch.autograd.Function):
+    """One adapter branch of MemoryEfficientCrossAttention(add_lora=True) (attention.py:373-376,421-424):
+    base_out + dropout_p(up(down(x))).  Forward: t = x D^T on cd360_gemm_bf16 (N = r), then cd360_lowrank_add_bf16 with the mask drawn
+    in the kernel.  Saves x, t (rank r) and the mask key (a copy of the (seed, offset) pair and the site), never the mask.  Backward:
+    g = dropout_apply(dy); dU = g^T t; dt = g U; dD = dt^T x; dx = dt D (cd360_lowrank_add_bf16 with base = NULL: K = r is below the
+    GEMM's K % 64); d base_out = dy."""
+
+    @staticmethod
+    def forward(ctx, x, base_out, down, up, p, site):
+        x2 = x.detach()
+        if x2.stride(-1) != 1:
+            x2 = x2.contiguous()
+        try:
+            ops._rows2d(x2)
+        except ops.Cd360Error:
+            x2 = x2.contiguous()
+        base = base_out.detach()
+        if not ops._aligned_rows(base):
+            base = base.contiguous()
+        t = ops.gemm(x2, down.detach().contiguous())
+        key = ops.dropout_state(x.device).clone() if p > 0 else None
+        out = ops.lowrank_add(t, up.detach().contiguous(), base=base, p=p, site=site, key=key)
+        ctx.save_for_backward(x2, t, down, up, key)
+        ctx.p, ctx.site = p, site
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, t, down, up, key = ctx.saved_tensors
+        r, K = down.shape
+        N = up.shape[0]
+        dy = dy.contiguous()
+        g = ops.dropout_apply(dy, ctx.p, ctx.site, key=key) if ctx.p > 0 else dy
+        g2, t2, x2 = g.reshape(-1, N), t.reshape(-1, r), x.reshape(-1, K)
+        dx = dD = dU = None
+        need_dt = ctx.needs_input_grad[0] or ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[3]:
+            dU = ops.gemm_tn(g2, t2).to(up.dtype)
+        if need_dt:
+            dt = ops.gemm(g2, ops.weight_t(up))  # [M, r] = g U, K = N
+            if ctx.needs_input_grad[2]:
+                dD = ops.gemm_tn(dt, x2).to(down.dtype)
+            if ctx.needs_input_grad[0]:
+                dx = ops.lowrank_add(dt, ops.weight_t(down)).reshape(x.shape)
+        return dx, (dy if ctx.needs_input_grad[1] else None), dD, dU, None, None
+
+
+def lora(x, base_out, down, up, p, site):
+    return LoraFn.apply(x, base_out, down, up, p, site)

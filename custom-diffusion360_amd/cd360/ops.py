@@ -1201,3 +1201,119 @@ def out_conv4(x: torch.Tensor, w36: torch.Tensor, bias: torch.Tensor, N: int, H:
     with _timed("conv_igemm", 2.0 * N * H * W * 9 * cin * 4, 2.0 * (N * H * W * (cin + 4) + 36 * cin)):
         check(_lib.load().cd360_out_conv4_bf16(_ptr(x), _ptr(w36), _ptr(bias), _ptr(out), N, H, W, cin, _stream()), "cd360_out_conv4_bf16")
     return out
+
+
+# ----------------------------------------------------------------------------------------------- rank-r adapters (add_lora=True)
+LOWRANK_RANKS = (16, 32, 64)
+_DROPOUT_STATE = {}  # device -> int64 [2] (seed, offset) read by the mask of cd360_lowrank_add_bf16 / cd360_dropout_apply_bf16
+_DROPOUT_DRAW = [0]  # host-side draw index of the current step: every mask drawn in a step gets its own site
+
+
+def dropout_state(device) -> torch.Tensor:
+    """The (seed, offset) pair of the adapter dropout masks on `device` (int64 [2] in device memory).  The seed is drawn once from
+    torch's CPU generator (so torch.manual_seed decides it); the offset advances through dropout_tick()."""
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    st = _DROPOUT_STATE.get(dev)
+    if st is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        st = _DROPOUT_STATE[dev] = torch.tensor([seed, 0], dtype=torch.int64, device=dev)
+    return st
+
+
+def dropout_tick(device=None) -> None:
+    """Once per training step (finetune.train_step): advance the mask offset on the device (cd360_dropout_tick: a captured step draws
+    new masks on every replay) and restart the host-side draw index, so eager and replayed steps see the same site sequence."""
+    st = dropout_state(torch.device("cuda") if device is None else device)
+    check(_lib.load().cd360_dropout_tick(_ptr(st), _stream()), "cd360_dropout_tick")
+    _DROPOUT_DRAW[0] = 0
+
+
+def dropout_site(site: int) -> int:
+    """`site` (block x 8 + {attn1, attn2} x 4 + {q, k, v, o}) combined with the next draw index of the step."""
+    d = _DROPOUT_DRAW[0]
+    _DROPOUT_DRAW[0] = d + 1
+    return int(site) + (d << 24)
+
+
+def _aligned_rows(t: torch.Tensor) -> bool:
+    if not (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() >= 1 and t.stride(-1) == 1 and t.data_ptr() % 16 == 0):
+        return False
+    try:
+        _, ld = _rows2d(t)
+    except Cd360Error:
+        return False
+    return ld % 8 == 0
+
+
+def lowrank_add_ok(t: torch.Tensor, u: torch.Tensor, base: Optional[torch.Tensor] = None) -> bool:
+    """Shape envelope of cd360_lowrank_add_bf16: t [..., r] with r in LOWRANK_RANKS, u [N, r] with N % 16 == 0, base [..., N]; bf16 on the GPU,
+    16-byte aligned rows (strided column slices of a wider buffer are fine)."""
+    if not (u.dim() == 2 and t.shape[-1] in LOWRANK_RANKS and u.shape[1] == t.shape[-1] and u.shape[0] % 16 == 0):
+        return False
+    if not (_aligned_rows(t) and _aligned_rows(u)):
+        return False
+    return base is None or (_aligned_rows(base) and base.shape[-1] == u.shape[0] and base.shape[:-1] == t.shape[:-1])
+
+
+def lowrank_add(t: torch.Tensor, u: torch.Tensor, base: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, p: float = 0.0,
+                site: int = 0, key: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [..., N] = base + s * keep * (t [..., r] @ u [N, r]^T) on cd360_lowrank_add_bf16 (fp32 MFMA, one bf16 rounding).  base None reads
+    as zero; out may be base (in place) or any view with the same rows.  p > 0 applies the adapter dropout (keep drawn from `key`, an int64
+    (seed, offset) pair on the device -- dropout_state() by default -- and `site`; s = 1 / (1 - p)).  Not recorded by autograd (grad.LoraFn)."""
+    _need_gpu(t, u, base, out)
+    assert lowrank_add_ok(t, u, base), "cd360 lowrank_add: see lowrank_add_ok()"
+    M, ldt = _rows2d(t)
+    N, r = u.shape
+    if out is None:
+        out = torch.empty(*t.shape[:-1], N, dtype=torch.bfloat16, device=t.device)
+    assert _aligned_rows(out) and out.shape[-1] == N
+    mo, ldo = _rows2d(out)
+    ldb = 0
+    if base is not None:
+        mb, ldb = _rows2d(base)
+        assert mb == M
+    assert mo == M
+    if p > 0 and key is None:
+        key = dropout_state(t.device)
+    with _timed(_shape_tag("lowrank_add", M, N, r), 2.0 * M * N * r, 2.0 * (M * N * (2 if base is not None else 1) + M * r + N * r)):
+        check(_lib.load().cd360_lowrank_add_bf16(_ptr(base), ldb, _ptr(t), ldt, _ptr(u), u.stride(0), _ptr(out), ldo, M, N, r, float(p),
+                                                 _ptr(key) if p > 0 else None, int(site), _stream()), "cd360_lowrank_add_bf16")
+    return out
+
+
+def dropout_apply_ok(dy: torch.Tensor) -> bool:
+    return _aligned_rows(dy) and dy.shape[-1] % 8 == 0
+
+
+def dropout_apply(dy: torch.Tensor, p: float, site: int, key: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """s * keep * dy with the mask lowrank_add draws for the same (key, site, element) (cd360_dropout_apply_bf16): the adapter dropout's
+    backward."""
+    _need_gpu(dy, out)
+    assert dropout_apply_ok(dy) and 0.0 <= p < 1.0
+    M, ldd = _rows2d(dy)
+    N = dy.shape[-1]
+    if out is None:
+        out = torch.empty(*dy.shape[:-1], N, dtype=torch.bfloat16, device=dy.device)
+    mo, ldo = _rows2d(out)
+    assert mo == M and _aligned_rows(out)
+    if key is None:
+        key = dropout_state(dy.device)
+    with _timed("dropout_apply", 0.0, 4.0 * M * N):
+        check(_lib.load().cd360_dropout_apply_bf16(_ptr(dy), ldd, _ptr(out), ldo, M, N, float(p), _ptr(key), int(site), _stream()),
+              "cd360_dropout_apply_bf16")
+    return out
+
+
+def lora_ok(x: torch.Tensor, base_out: torch.Tensor, down: torch.Tensor, up: torch.Tensor) -> bool:
+    """grad.LoraFn can serve base_out + drop(x down^T up^T): the down GEMM (cd360_gemm_bf16, K = in % 64), the adapter add, and in the
+    backward the up-weight transpose GEMM (K = out % 64)."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and down.dtype == torch.bfloat16 and up.dtype == torch.bfloat16 and base_out.dtype == torch.bfloat16):
+        return False
+    r, K = down.shape
+    N = up.shape[0]
+    if up.shape[1] != r or r not in LOWRANK_RANKS or x.shape[-1] != K or base_out.shape[-1] != N:
+        return False
+    M = x.numel() // max(K, 1)
+    return gemm_ok(M, r, K) and gemm_ok(M, r, N) and N % 16 == 0 and base_out.stride(-1) == 1

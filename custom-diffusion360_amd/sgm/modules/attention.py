@@ -14,8 +14,9 @@ reference_attn/pose_emb_layers`) keep working.  What differs is underneath:
 
 The reference's `CrossAttention` ("softmax" mode) cannot be constructed by BasicTransformerBlock (it is passed an
 `add_lora` kwarg it does not accept, attention.py:214-222,495-503); here "softmax" maps to the same HIP attention.
-LoRA branches, `additional_tokens`, `n_times_crossframe_attn_in_self`, `disable_self_attn`, conv proj_in/out and
-are not exercised by the shipped config and raise NotImplementedError (`average=True` is served: uniform view weights).
+`additional_tokens`, `n_times_crossframe_attn_in_self`, `disable_self_attn` and conv proj_in/out are not exercised by the shipped config
+ and raise NotImplementedError (`average=True` is served: uniform view weights).  The rank-32 attention adapters
+(`add_lora=True`) are served: see MemoryEfficientCrossAttention.
 """
 from __future__ import annotations
 
@@ -28,7 +29,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from cd360 import memo, ops, routes, sample_py_patch
+from cd360 import grad, memo, ops, routes, sample_py_patch
 from ..modules.diffusionmodules.util import HipLayerNorm, HipLinear, checkpoint, group_norm_tokens, tag_gn_stats, tokens_to_image, zero_module  # noqa: F401
 from ..modules.nerfsd_pytorch3d import NerfSDModule, VolRender
 from ..util import default, exists
@@ -181,13 +182,21 @@ def _pad_tokens(ctx: torch.Tensor, mult: int = 8) -> torch.Tensor:
     return _PADDED.get(ctx, lambda: F.pad(ctx, (0, 0, 0, pad)), extra=mult)
 
 
+LORA_RANK = 32  # attention.py:331
+_LORA_SITES = [0]
+
+
+def _next_lora_site() -> int:
+    """Mask site of a new adapter-carrying module: 8 per pose block ({attn1, attn2} x 4 + {q, k, v, o}), in construction order."""
+    _LORA_SITES[0] += 1
+    return 8 * _LORA_SITES[0]
+
+
 class MemoryEfficientCrossAttention(nn.Module):
     """to_q / to_k / to_v / to_out.0 exactly as the reference (attention.py:305-425); forward on the HIP kernel."""
 
     def __init__(self, query_dim, context_dim=None, heads=8, dim_head=64, dropout=0.0, add_lora=False, **kwargs):
         super().__init__()
-        if add_lora:
-            raise NotImplementedError("add_lora=True is not exercised by the shipped config (yaml:50)")
         if dim_head != 64:
             raise NotImplementedError("the HIP attention kernel is specialised for head dim 64 (SDXL)")
         inner_dim = dim_head * heads
@@ -197,22 +206,90 @@ class MemoryEfficientCrossAttention(nn.Module):
         self.to_k = HipLinear(context_dim, inner_dim, bias=False)
         self.to_v = HipLinear(context_dim, inner_dim, bias=False)
         self.to_out = nn.Sequential(HipLinear(inner_dim, query_dim), nn.Dropout(dropout))
+        if add_lora:  # rank-32 adapters, registered and initialised as the reference (attention.py:330-347)
+            r = LORA_RANK
+            self.to_q_attn3_down = nn.Linear(query_dim, r, bias=False)
+            self.to_q_attn3_up = zero_module(nn.Linear(r, inner_dim, bias=False))
+            self.to_k_attn3_down = nn.Linear(context_dim, r, bias=False)
+            self.to_k_attn3_up = zero_module(nn.Linear(r, inner_dim, bias=False))
+            self.to_v_attn3_down = nn.Linear(context_dim, r, bias=False)
+            self.to_v_attn3_up = zero_module(nn.Linear(r, inner_dim, bias=False))
+            self.to_o_attn3_down = nn.Linear(inner_dim, r, bias=False)
+            self.to_o_attn3_up = zero_module(nn.Linear(r, query_dim, bias=False))
+            self.dropoutq = nn.Dropout(0.1)
+            self.dropoutk = nn.Dropout(0.1)
+            self.dropoutv = nn.Dropout(0.1)
+            self.dropouto = nn.Dropout(0.1)
+            for w in "qkvo":
+                nn.init.normal_(getattr(self, f"to_{w}_attn3_down").weight, std=1 / r)
+            self._lora_site = _next_lora_site()  # mask site of the adapter dropouts; BasicTransformerBlock renumbers it per block
         self.attention_op = None
         self._merged = {}
         self._kv_cache = None
         self._kv8_cache = None  # fp8 image of the cached K / V (context_fp8)
         self.cache_context_kv = False
 
+    # ---- adapters (add_lora=True) -----------------------------------------------------------------------------------------------------------
+    # Module / autograd route: every adapter is a branch of its own, base + dropout(up(down(x))), on grad.LoraFn (down GEMM + the rank-r add
+    # of cd360_lowrank_add_bf16 with the mask drawn in the kernel) -- or torch's F.linear / dropout outside the kernels' envelope (CPU, fp32).
+    # Without a tape and with every adapter dropout inactive the adapters are folded into the projection weights instead, W' = W + U D in
+    # fp32 before the one bf16 rounding (`lora_folded`, the fused block's packs, the cached context K / V): the same arithmetic at no per-step cost.
+    def _lora_mods(self, w: str):
+        return getattr(self, f"to_{w}_attn3_down"), getattr(self, f"to_{w}_attn3_up"), getattr(self, f"dropout{w}")
+
+    def lora_params(self):
+        return [getattr(self, f"to_{w}_attn3_{d}").weight for w in "qkvo" for d in ("down", "up")] if self.add_lora else []
+
+    def lora_dropout_active(self) -> bool:
+        return self.add_lora and any(d.training and d.p > 0 for d in (self.dropoutq, self.dropoutk, self.dropoutv, self.dropouto))
+
+    def lora_merge(self) -> bool:
+        """True when the adapters are folded into the projection weights (no tape over any of them, no adapter dropout drawing)."""
+        if not self.add_lora or self.lora_dropout_active():
+            return False
+        return not (torch.is_grad_enabled() and any(p.requires_grad for p in self.lora_params() + [self.to_q.weight, self.to_k.weight,
+                                                                                                   self.to_v.weight, self.to_out[0].weight]))
+
+    def lora_key(self):
+        return tuple((p.data_ptr(), p._version) for p in self.lora_params())
+
+    def lora_folded(self, w: str, base: torch.Tensor) -> torch.Tensor:
+        """fp32 W + U D of projection `w` (q / k / v / o) for the base weight `base` (plain W when there are no adapters)."""
+        base = base.detach().float()
+        if not self.add_lora:
+            return base
+        down, up, _ = self._lora_mods(w)
+        return base + up.weight.detach().float() @ down.weight.detach().float()
+
+    def _lora(self, w: str, x: torch.Tensor, base: torch.Tensor) -> torch.Tensor:
+        """base + dropout_w(up_w(down_w(x))) (attention.py:373-376,421-424)."""
+        down, up, drop = self._lora_mods(w)
+        p = drop.p if drop.training else 0.0
+        if ops.lora_ok(x, base, down.weight, up.weight) and not routes.library_linear:
+            return grad.lora(x, base, down.weight, up.weight, p, ops.dropout_site(self._lora_site + "qkvo".index(w)))
+        return base + drop(F.linear(F.linear(x, down.weight), up.weight))
+
     def _merged_weight(self, which: str):
         """Row-concatenated projection weights, rebuilt when any of them changes: "qkv" = [to_q; to_k; to_v] for self-attention
-        (one GEMM, N = 3 inner), "kv" = [to_k; to_v] for a cross-attention context."""
-        mods = (self.to_q, self.to_k, self.to_v) if which == "qkv" else (self.to_k, self.to_v)
-        key = tuple((m.weight.data_ptr(), m.weight._version) for m in mods) + (mods[0].weight.dtype, mods[0].weight.device)
-        if torch.is_grad_enabled() and any(m.weight.requires_grad for m in mods):  # trainkeys poseattn: stay on the autograd tape
+        (one GEMM, N = 3 inner), "kv" = [to_k; to_v] for a cross-attention context, "q" / "o" = to_q / to_out.0 alone.  With lora_merge()
+        the adapters are folded in (fp32, one rounding); otherwise the adapter branches are the caller's."""
+        names = {"qkv": "qkv", "kv": "kv", "q": "q", "o": "o"}[which]
+        mods = [{"q": self.to_q, "k": self.to_k, "v": self.to_v, "o": self.to_out[0]}[w] for w in names]
+        merge = self.lora_merge()
+        if not merge and len(mods) == 1:
+            return mods[0].weight
+        key = tuple((m.weight.data_ptr(), m.weight._version) for m in mods) + (mods[0].weight.dtype, mods[0].weight.device, merge)
+        if merge:
+            key = key + self.lora_key()
+        elif torch.is_grad_enabled() and any(m.weight.requires_grad for m in mods):  # trainkeys poseattn: stay on the autograd tape
             return torch.cat([m.weight for m in mods], 0)
         cache = self._merged.get(which)
         if cache is None or cache[0] != key:
-            cache = (key, torch.cat([m.weight.detach() for m in mods], 0).contiguous())
+            if merge:
+                w = torch.cat([self.lora_folded(n, m.weight) for n, m in zip(names, mods)], 0).to(mods[0].weight.dtype).contiguous()
+            else:
+                w = torch.cat([m.weight.detach() for m in mods], 0).contiguous()
+            cache = (key, w)
             self._merged[which] = cache
         return cache[1]
 
@@ -223,16 +300,20 @@ class MemoryEfficientCrossAttention(nn.Module):
         # caller opts in (cd360.sampling.enable_reference_sampling(cache_context=True): "this context buffer stays put until
         # clear_rendered_feat()"), the projections are kept resident and reused by every step and by the pose-token attention.
         wk, wv = self.to_k.weight, self.to_v.weight
-        use_cache = self.cache_context_kv and not torch.is_grad_enabled()
-        if use_cache:
-            key = (context.data_ptr(), context._version, tuple(context.shape), context.dtype, wk.data_ptr(), wk._version, wv.data_ptr(), wv._version)
+        use_cache = self.cache_context_kv and not torch.is_grad_enabled() and not self.lora_dropout_active()
+        if use_cache:  # the adapter weights are part of the key: an optimizer step or load_state_dict on them reaches the next forward
+            key = (context.data_ptr(), context._version, tuple(context.shape), context.dtype, wk.data_ptr(), wk._version, wv.data_ptr(), wv._version,
+                   self.lora_key())
             if self._kv_cache is not None and self._kv_cache[0] == key:
                 return self._kv_cache[1]
         inner = self.heads * self.dim_head
         ctx = _pad_tokens(context)
         wkv = self._merged_weight("kv")
         kv = _linear(ctx, wkv)  # the same hand-written GEMM as the rest of the block
-        out = (kv[..., :inner], kv[..., inner:], context.shape[1])
+        k, v = kv[..., :inner], kv[..., inner:]
+        if self.add_lora and not self.lora_merge():  # padded context rows are zero: their adapter outputs are zero too
+            k, v = self._lora("k", ctx, k), self._lora("v", ctx, v)
+        out = (k, v, context.shape[1])
         # the keyed tensors are held by the entry: their addresses cannot be recycled for other content while the entry is alive
         self._kv_cache = (key, out, (context, wk, wv)) if use_cache else None
         return out
@@ -251,7 +332,9 @@ class MemoryEfficientCrossAttention(nn.Module):
     def attend(self, x: torch.Tensor, kv) -> torch.Tensor:
         """softmax(q k^T / sqrt(d)) v and the output projection for precomputed (k, v, nk)."""
         k, v, nk = kv
-        q = _linear(x, self.to_q.weight)
+        q = _linear(x, self._merged_weight("q"))
+        if self.add_lora and not self.lora_merge():
+            q = self._lora("q", x, q)
         return self._finish(x, q, k, v, nk)
 
     def _finish(self, x, q, k, v, nk):
@@ -261,20 +344,37 @@ class MemoryEfficientCrossAttention(nn.Module):
         out = ops.attention(q, k, v, self.heads, nk)
         if dt != torch.bfloat16:
             out = out.to(dt)
-        return self.to_out(out)
+        if not self.add_lora:
+            return self.to_out(out)
+        if self.lora_merge():
+            return self.to_out[1](_linear(out, self._merged_weight("o"), self.to_out[0].bias))
+        return self._lora("o", out, self.to_out(out))  # final = to_out(out) + dropouto(up_o(down_o(out))) (attention.py:421-424)
 
     def forward(self, x, context=None, mask=None, additional_tokens=None, n_times_crossframe_attn_in_self=0):
         if additional_tokens is not None or n_times_crossframe_attn_in_self:
             raise NotImplementedError("additional_tokens / cross-frame attention are not used by the shipped config")
         if exists(mask):
             raise NotImplementedError  # as the reference (attention.py:411-412)
-        if _watched(self.to_q, self.to_k, self.to_v):  # observers on the projections: the reference's call sequence (attention.py:368-372)
+        lora_mods = [m for w in ("qkvo" if self.add_lora else "") for m in self._lora_mods(w)]
+        if _watched(self.to_q, self.to_k, self.to_v, *lora_mods):  # observers: the reference's call sequence (attention.py:368-376,421-424)
             ctx = _pad_tokens(default(context, x))
-            return self._finish(x, self.to_q(x), self.to_k(ctx), self.to_v(ctx), default(context, x).shape[1])
+            q, k, v = self.to_q(x), self.to_k(ctx), self.to_v(ctx)
+            if not self.add_lora:
+                return self._finish(x, q, k, v, default(context, x).shape[1])
+            q = q + self.dropoutq(self.to_q_attn3_up(self.to_q_attn3_down(x)))
+            k = k + self.dropoutk(self.to_k_attn3_up(self.to_k_attn3_down(ctx)))
+            v = v + self.dropoutv(self.to_v_attn3_up(self.to_v_attn3_down(ctx)))
+            out = ops.attention(q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16), self.heads, default(context, x).shape[1]).to(x.dtype)
+            return self.to_out(out) + self.dropouto(self.to_o_attn3_up(self.to_o_attn3_down(out)))
+        if context is None and self.add_lora and not self.lora_merge():  # adapter branches on the q / k / v column slices of one GEMM
+            inner = self.heads * self.dim_head
+            qkv = _linear(x, self._merged_weight("qkv"))
+            q, k, v = (self._lora(w, x, qkv[..., i * inner:(i + 1) * inner]) for i, w in enumerate("qkv"))
+            return self._finish(x, q, k, v, x.shape[1])
         if context is None:  # self-attention: q, k, v are the three column slices of one GEMM, read in place by the kernel
             inner = self.heads * self.dim_head
             qkv = _linear(x, self._merged_weight("qkv"))
-            if qkv.dtype == torch.bfloat16 and qkv.requires_grad and torch.is_grad_enabled():
+            if qkv.dtype == torch.bfloat16 and qkv.requires_grad and torch.is_grad_enabled() and not self.add_lora:
                 return self.to_out(ops.self_attention_qkv(qkv, self.heads))  # training: one d(q|k|v) buffer written by the backward kernel
             return self._finish(x, qkv[..., :inner], qkv[..., inner:2 * inner], qkv[..., 2 * inner:], x.shape[1])
         return self.attend(x, self.project_context(context))
@@ -305,6 +405,9 @@ class BasicTransformerBlock(nn.Module):
         self.ff = FeedForward(dim, dropout=dropout, glu=gated_ff)
         self.attn2 = attn_cls(query_dim=dim, context_dim=context_dim, heads=n_heads, dim_head=d_head, dropout=dropout, add_lora=add_lora,
                               backend=sdp_backend)
+        if add_lora:  # mask sites of the adapter dropouts: block x 8 + {attn1, attn2} x 4 + {q, k, v, o}
+            site = _next_lora_site()
+            self.attn1._lora_site, self.attn2._lora_site = site, site + 4
         if image_cross:
             self.pose_emb_layers = HipLinear(2 * dim, dim, bias=False)
             nn.init.eye_(self.pose_emb_layers.weight)
@@ -496,7 +599,7 @@ class BasicTransformerBlock(nn.Module):
             hip_ln = tok.is_cuda and tok.dtype == torch.bfloat16 and self.norm2.weight.dtype == torch.bfloat16 and C <= 2048
             a2 = self.attn2
             lin = a2.to_out[0]
-            if (hip_ln and not _watched(a2) and not (self.training and a2.to_out[1].p > 0) and lin.bias is not None
+            if (hip_ln and not _watched(a2) and not (self.training and a2.to_out[1].p > 0) and lin.bias is not None and not a2.add_lora
                     and ops.linear_ok(tok, lin.weight) and not routes.library_linear and not routes.no_train_fusions):
                 # training: the residual rides through the two GEMM-side operators instead of two passes over the [b hw S, C] tokens --
                 # the LayerNorm hands `tok` on as an alias whose gradient its backward kernel adds itself, the out projection takes it
@@ -582,7 +685,8 @@ class BasicTransformerBlock(nn.Module):
         return (is_cuda and dtype == torch.bfloat16 and not torch.is_grad_enabled() and self.norm1.weight.dtype == torch.bfloat16
                 and c % 64 == 0 and isinstance(self.ff.net[0], GEGLU) and not routes.library_linear
                 and ops.gemm_ok(rows, c, c)  # 32-bit buffer offsets of the GEMM core: a larger batch takes the module route
-                and not (self.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in (self.attn1.to_out[1], self.attn2.to_out[1], self.ff.net[1]))))
+                and not (self.training and any(isinstance(m, nn.Dropout) and m.p > 0 for m in (self.attn1.to_out[1], self.attn2.to_out[1], self.ff.net[1])))
+                and not self.attn1.lora_dropout_active() and not self.attn2.lora_dropout_active())  # adapters drawing masks: module route
 
     def _packed(self):
         """Weights in the form the fused GEMM epilogues want, rebuilt when any source parameter changes:
@@ -593,7 +697,7 @@ class BasicTransformerBlock(nn.Module):
                a1.to_q.weight, a1.to_k.weight, a1.to_v.weight, a1.to_out[0].weight, a1.to_out[0].bias,
                a2.to_q.weight, a2.to_out[0].weight, a2.to_out[0].bias,
                ff.net[0].proj.weight, ff.net[0].proj.bias, ff.net[2].weight, ff.net[2].bias]
-        key = tuple((t.data_ptr(), t._version) for t in src)
+        key = tuple((t.data_ptr(), t._version) for t in src + a1.lora_params() + a2.lora_params())  # adapters are folded into the packs
         if self._pack is not None and self._pack[0] == key:
             P = self._pack[1]
             if self.image_cross:  # the one trainable source ("pose" keys): re-packed alone, the frozen entries stay (fine-tune step)
@@ -605,11 +709,12 @@ class BasicTransformerBlock(nn.Module):
             return P
         P = {}
         # the q rows carry the softmax scale and log2(e) (ops.attention(prescaled=True)): q is rounded to bf16 once, as in the reference
-        P["qkv"] = ops.pack_ln_linear(torch.cat([a1.to_q.weight.detach().float() * ops.ATTN_PRESCALE, a1.to_k.weight.detach().float(),
-                                                 a1.to_v.weight.detach().float()], 0), None, self.norm1.weight, self.norm1.bias)
-        P["o1"] = (a1.to_out[0].weight.detach().to(torch.bfloat16).contiguous(), a1.to_out[0].bias.detach().float().contiguous())
-        P["q2"] = ops.pack_ln_linear(a2.to_q.weight, None, self.norm2.weight, self.norm2.bias)
-        P["o2"] = (a2.to_out[0].weight.detach().to(torch.bfloat16).contiguous(), a2.to_out[0].bias.detach().float().contiguous())
+        # add_lora: W' = W + U D per projection (MemoryEfficientCrossAttention.lora_folded), in fp32 before the packs' one rounding
+        P["qkv"] = ops.pack_ln_linear(torch.cat([a1.lora_folded("q", a1.to_q.weight) * ops.ATTN_PRESCALE, a1.lora_folded("k", a1.to_k.weight),
+                                                 a1.lora_folded("v", a1.to_v.weight)], 0), None, self.norm1.weight, self.norm1.bias)
+        P["o1"] = (a1.lora_folded("o", a1.to_out[0].weight).to(torch.bfloat16).contiguous(), a1.to_out[0].bias.detach().float().contiguous())
+        P["q2"] = ops.pack_ln_linear(a2.lora_folded("q", a2.to_q.weight), None, self.norm2.weight, self.norm2.bias)
+        P["o2"] = (a2.lora_folded("o", a2.to_out[0].weight).to(torch.bfloat16).contiguous(), a2.to_out[0].bias.detach().float().contiguous())
         w, ws, cb = ops.pack_ln_linear(ff.net[0].proj.weight, ff.net[0].proj.bias, self.norm3.weight, self.norm3.bias)
         perm = ops.geglu_row_order(w.shape[0] // 2, w.device)
         P["ff1"] = (w[perm].contiguous(), ws[perm].contiguous(), cb[perm].contiguous())

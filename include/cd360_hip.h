@@ -470,6 +470,25 @@ int cd360_adamw_bf16(int n, const void* const* grads, void* const* params, const
  * tensor that did not come out of cd360_gemm_bf16 (C % 8 == 0). */
 int cd360_row_stats_bf16(const void* x, void* stats, int64_t rows, int C, int64_t ld, void* stream);
 
+/* ---- Rank-r adapters of the pose blocks' attention (add_lora=True) ------------------------------------------------------------
+ * replaces `q += dropoutq(to_q_attn3_up(to_q_attn3_down(x)))` and its k / v / o forms (sgm/modules/attention.py:330-347 adapter Linears,
+ *          r = 32, up weights zero-initialised; :373-376 q / k / v; :421-424 `final = to_out(out) + dropouto(up_o(down_o(out)))`; only the
+ *          attn1 / attn2 of image_cross blocks carry them, :775, :500, :511).
+ * out[M, N] = base[M, N] + s * keep(i, j) * (T[M, r] @ U[N, r]^T): T = x D^T (the down projection, from cd360_gemm_bf16), U = the up
+ * weight [N, r] (nn.Linear layout).  r in {16, 32, 64}; all bf16 with element row strides (multiples of 8, >= the row width), 16-byte
+ * aligned pointers, N % 16 == 0: column slices of a q|k|v buffer are addressed in place.  out may alias base; base NULL reads as zero
+ * (with base = NULL the same entry is the data gradient dX = dY W of a Linear whose output width r is below the GEMM's K % 64).
+ * fp32 MFMA accumulation, rounded to bf16 once after the add.  Dropout: p = 0 means no mask and s = 1; 0 < p < 1 draws keep(i, j) with
+ * probability 1 - p and s = 1 / (1 - p).  keep is a pure counter-based hash of rng_state = int64 (seed, offset) in device memory (8-byte
+ * aligned), the host-side `site` id and (i, j): the forward and the backward of one step regenerate the same mask, nothing is stored.
+ * cd360_dropout_apply_bf16: out = s * keep(i, j) * dy, the mask's backward (N % 8 == 0).  cd360_dropout_tick adds 1 to the offset:
+ * once per training step, so that a hipGraph replay of the step draws new masks. */
+int cd360_lowrank_add_bf16(const void* base, int64_t ldb, const void* t, int64_t ldt, const void* u, int64_t ldu, void* out, int64_t ldo,
+                           int64_t M, int N, int r, float p, const void* rng_state, int64_t site, void* stream);
+int cd360_dropout_apply_bf16(const void* dy, int64_t ldd, void* out, int64_t ldo, int64_t M, int N, float p, const void* rng_state,
+                             int64_t site, void* stream);
+int cd360_dropout_tick(void* rng_state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
