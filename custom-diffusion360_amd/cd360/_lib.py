@@ -24,6 +24,12 @@ SIGNATURES = {
     "cd360_attn_fwd_lse_bf16": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _I64P, _I64P, _I64P, _I64P, c_float, _P]),
     "cd360_attn_bwd_bf16": (c_int, [_P] * 10 + [c_int] * 4 + [_I64P] * 8 + [c_float, _P]),
     "cd360_attn_fwd_xformers_bf16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, _P]),
+    "cd360_attn_single_splits": (c_int, [c_int, c_int]),
+    "cd360_attn_single_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "cd360_attn_single_bf16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _I64P, _I64P, _I64P, _I64P, c_float, _P, _P]),
+    "cd360_vae_conv_in_stats_slabs": (c_int, [c_int, c_int]),
+    "cd360_vae_conv_in_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "cd360_vae_conv_out_bf16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "cd360_patch_rays": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "cd360_ray_project_index": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "cd360_sample_pdf": (c_int, [_P, _P, _P, _P, _P, c_float, c_int64, c_int, c_int, _P]),

@@ -216,14 +216,47 @@ def memory_efficient_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
     _need_gpu(q, k, v)
     bh, nq, d = q.shape
     nk = k.shape[1]
+    if d != 64 and d % 64 == 0 and d <= 512 and nk == nq:
+        # the first stage's single-head attention (sgm/modules/diffusionmodules/model.py:248-250: [B, H W, C], C = 512 at SDXL widths)
+        dt = q.dtype
+        q, k, v = (t.to(torch.bfloat16).contiguous() for t in (q, k, v))
+        return attention_single(q, k, v, qscale=d ** -0.5 * 1.4426950408889634).to(dt)
     if d != 64:
-        raise Cd360Error(f"head dim {d} unsupported (SDXL uses 64)")
+        raise Cd360Error(f"head dim {d} unsupported (SDXL uses 64; single-head self-attention takes 128 .. 512 in steps of 64)")
     dt = q.dtype
     q, k, v = (t.to(torch.bfloat16).contiguous() for t in (q, k, v))
     out = torch.empty_like(q)
     check(_lib.load().cd360_attn_fwd_xformers_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), bh, nq, nk, 64 ** -0.5, _stream()),
           "cd360_attn_fwd_xformers_bf16")
     return out.to(dt)
+
+
+_I64x2 = ctypes.c_int64 * 2
+
+
+def attention_single_splits(b: int, n: int) -> int:
+    """Key splits cd360_attn_single_bf16 uses for b images of n pixels (1: one launch, no combine)."""
+    return _lib.load().cd360_attn_single_splits(b, n)
+
+
+def attention_single(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, qscale: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Single-head self-attention at head dim C (the first stage's mid-block attention, model.py:204-265): q, k, v [b, N, C] bf16
+    (C % 64 == 0, C <= 512; last dim contiguous, row / batch strides free: e.g. the column slices of one merged q|k|v projection) ->
+    [b, N, C] = softmax_2(qscale q k^T) v.  qscale = 1: q already carries C^-0.5 log2 e (pack_attn_qkv_weight).  Forward only."""
+    _need_gpu(q, k, v)
+    b, n, c = q.shape
+    assert q.dtype == k.dtype == v.dtype == torch.bfloat16 and k.shape == q.shape and v.shape == q.shape
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1
+    if out is None:
+        out = torch.empty(b, n, c, dtype=torch.bfloat16, device=q.device)
+    lib = _lib.load()
+    nbytes = lib.cd360_attn_single_workspace_bytes(b, n, c)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device) if nbytes > 0 else None
+    st = lambda t: _I64x2(t.stride(0), t.stride(1))
+    with _timed("attn_single", 4.0 * b * n * n * c, 2.0 * 4 * b * n * c):
+        check(lib.cd360_attn_single_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), b, n, c, st(q), st(k), st(v), st(out), float(qscale), _ptr(ws),
+                                         _stream()), "cd360_attn_single_bf16")
+    return out
 
 
 # ----------------------------------------------------------------------------------------------- rays / projection
@@ -1200,6 +1233,66 @@ def out_conv4(x: torch.Tensor, w36: torch.Tensor, bias: torch.Tensor, N: int, H:
     out = torch.empty(N, H * W, 4, dtype=torch.bfloat16, device=x.device)
     with _timed("conv_igemm", 2.0 * N * H * W * 9 * cin * 4, 2.0 * (N * H * W * (cin + 4) + 36 * cin)):
         check(_lib.load().cd360_out_conv4_bf16(_ptr(x), _ptr(w36), _ptr(bias), _ptr(out), N, H, W, cin, _stream()), "cd360_out_conv4_bf16")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------- the first stage's two ends (Decoder)
+def pack_vae_conv_in_weight(w: torch.Tensor) -> torch.Tensor:
+    """Decoder.conv_in weight [Cout, Cz, 3, 3] -> fp32 [Cz * 9, Cout], row ci * 9 + 3 ky + kx (cd360_vae_conv_in_f32)."""
+    cout, cz, kh, kw = w.shape
+    assert kh == 3 and kw == 3
+    return w.detach().float().permute(1, 2, 3, 0).reshape(cz * 9, cout).contiguous()
+
+
+def pack_vae_conv_out_weight(w: torch.Tensor) -> torch.Tensor:
+    """Decoder.conv_out weight [Cout <= 4, Cin, 3, 3] -> fp32 [9, Cin, 4] (tap 3 ky + kx, channel, output channel; columns >= Cout zero)
+    (cd360_vae_conv_out_bf16)."""
+    cout, cin, kh, kw = w.shape
+    assert kh == 3 and kw == 3 and cout <= 4
+    out = torch.zeros(9, cin, 4, dtype=torch.float32, device=w.device)
+    out[:, :, :cout] = w.detach().float().permute(2, 3, 1, 0).reshape(9, cin, cout)
+    return out
+
+
+def pack_attn_qkv(qw: torch.Tensor, qb: torch.Tensor, kw: torch.Tensor, kb: torch.Tensor, vw: torch.Tensor, vb: torch.Tensor):
+    """The q, k, v 1 x 1 convolutions of a first-stage attention block ([C, C, 1, 1] weights, [C] biases) -> (w bf16 [3 C, C], bias fp32
+    [3 C]) of ONE merged projection whose q rows and q bias carry C^-0.5 log2 e (multiplied in fp32, one bf16 rounding of the weight):
+    the prescaled q of attention_single(..., qscale=1)."""
+    c = qw.shape[0]
+    s = c ** -0.5 * 1.4426950408889634
+    w = torch.cat([qw.detach().float().reshape(c, c) * s, kw.detach().float().reshape(c, c), vw.detach().float().reshape(c, c)], 0)
+    b = torch.cat([qb.detach().float() * s, kb.detach().float(), vb.detach().float()], 0)
+    return w.to(torch.bfloat16).contiguous(), b.contiguous()
+
+
+def vae_conv_in(z: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], want_stats: bool = False):
+    """Decoder.conv_in: z fp32 NCHW [B, Cz, H, W] -> bf16 channels-last [B, H W, Cout] (cd360_vae_conv_in_f32).  want_stats=True
+    (H W % 64 == 0): returns (out, tile_stats [B, slabs, Cout, 2] fp32) for gn_silu(out, ..., tile_stats=tile_stats)."""
+    _need_gpu(z, w_packed, bias)
+    B, cz, H, W = z.shape
+    cout = w_packed.shape[1]
+    assert z.dtype == torch.float32 and z.is_contiguous() and w_packed.dtype == torch.float32 and w_packed.shape == (cz * 9, cout)
+    assert w_packed.is_contiguous() and (bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == cout))
+    lib = _lib.load()
+    out = torch.empty(B, H * W, cout, dtype=torch.bfloat16, device=z.device)
+    stats = torch.empty(B, lib.cd360_vae_conv_in_stats_slabs(H, W), cout, 2, dtype=torch.float32, device=z.device) if want_stats else None
+    with _timed("vae_conv_in", 2.0 * B * H * W * 9 * cz * cout, 4.0 * B * H * W * cz + 2.0 * B * H * W * cout):
+        check(lib.cd360_vae_conv_in_f32(_ptr(z), _ptr(w_packed), _ptr(bias), _ptr(out), _ptr(stats), B, cz, H, W, cout, _stream()),
+              "cd360_vae_conv_in_f32")
+    return (out, stats) if want_stats else out
+
+
+def vae_conv_out(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], N: int, H: int, W: int, cout: int) -> torch.Tensor:
+    """Decoder.conv_out: x bf16 channels-last [N, H W, Cin] (after norm_out + SiLU) -> fp32 NCHW [N, cout, H, W] (cd360_vae_conv_out_bf16)."""
+    _need_gpu(x, w_packed, bias)
+    cin = x.shape[-1]
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and x.numel() == N * H * W * cin and 1 <= cout <= 4
+    assert w_packed.dtype == torch.float32 and w_packed.is_contiguous() and w_packed.shape == (9, cin, 4)
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == cout)
+    out = torch.empty(N, cout, H, W, dtype=torch.float32, device=x.device)
+    with _timed("vae_conv_out", 2.0 * N * H * W * 9 * cin * cout, 2.0 * N * H * W * cin + 4.0 * N * H * W * cout):
+        check(_lib.load().cd360_vae_conv_out_bf16(_ptr(x), _ptr(w_packed), _ptr(bias), _ptr(out), N, H, W, cin, cout, _stream()),
+              "cd360_vae_conv_out_bf16")
     return out
 
 

@@ -1,0 +1,404 @@
+"""The first stage's autoencoder network (reference sgm/modules/diffusionmodules/model.py) on the HIP kernels: `Decoder` serves
+`AutoencoderKL.decode` (sgm/models/autoencoder.py:295-296, diffusion.py:208-212), so `decode_first_stage` runs without xformers.
+
+Constructors, attribute names and state_dict keys are the reference's, so checkpoints load unchanged.  Activations travel between the
+submodules as NCHW-shaped bf16 tensors in torch.channels_last memory format -- physically the channels-last rows [N, H W, C] the kernels
+read and write, no copy -- and every forward keeps the reference's call contract (NCHW in, NCHW out; a forward hook sees real values).
+A submodule called on its own with another dtype or layout converts its input once.  Kernel map:
+
+  ResnetBlock       gn_silu -> conv 3x3 (emits the GroupNorm slab sums) -> gn_silu on those sums -> conv 3x3 + residual
+                    (x, or the nin_shortcut 1x1 / conv_shortcut 3x3 output when in != out)
+  Attn blocks       GroupNorm -> ONE q|k|v 1x1 GEMM (q rows prescaled) -> cd360_attn_single_bf16 -> proj_out 1x1 + residual x
+  Upsample          cd360_conv_up2x_bf16 (nearest 2x folded into four 2x2-tap phases)
+  Decoder ends      cd360_vae_conv_in_f32 (fp32 NCHW latent in) and norm_out + SiLU -> cd360_vae_conv_out_bf16 (fp32 NCHW out)
+
+Packed weights are cached per module, keyed on the parameters' (data_ptr, _version): load_state_dict or an in-place copy_ repacks.
+An edit through `p.data` is NOT seen: `.data` is a tensor with a version counter of its own (as for UNetModel._emb_cat).
+Forward only: a call autograd would have to record raises (decode_first_stage runs under no_grad).  Encoder is constructible (so that
+AutoencoderKL.__init__ works and checkpoints load); its forward is not implemented."""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from cd360 import ops
+
+_INT32_BYTES = 2 ** 31  # the convolution cores address one operand with 32-bit byte offsets (cd360_conv_igemm_bf16)
+
+
+def nonlinearity(x):
+    # swish
+    return x * torch.sigmoid(x)
+
+
+def Normalize(in_channels, num_groups=32):
+    return torch.nn.GroupNorm(num_groups=num_groups, num_channels=in_channels, eps=1e-6, affine=True)
+
+
+# ----------------------------------------------------------------------------------------------- layout / cache helpers
+def _check_no_grad(mod: nn.Module) -> None:
+    if torch.is_grad_enabled() and any(p.requires_grad for p in mod.parameters()):
+        raise NotImplementedError("the first-stage HIP modules have no backward; call them under torch.no_grad() (decode_first_stage does)")
+
+
+def _rows(x: torch.Tensor):
+    """NCHW-shaped x -> (channels-last bf16 rows [N, H W, C], N, C, H, W); converts once unless x already is bf16 channels_last on the GPU."""
+    if not x.is_cuda:
+        raise ops.Cd360Error("the first-stage HIP modules run only on the GPU; got a CPU tensor")
+    n, c, h, w = x.shape
+    if x.dtype != torch.bfloat16 or not x.is_contiguous(memory_format=torch.channels_last):
+        x = x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    return x.permute(0, 2, 3, 1).reshape(n, h * w, c), n, c, h, w
+
+
+def _nchw(rows: torch.Tensor, n: int, h: int, w: int) -> torch.Tensor:
+    """[N, H W, C] contiguous rows -> the NCHW-shaped channels_last view of the same memory."""
+    return rows.view(n, h, w, rows.shape[-1]).permute(0, 3, 1, 2)
+
+
+def _with_stats(t: torch.Tensor, stats) -> torch.Tensor:
+    """Attach the GroupNorm slab sums a kernel produced while writing t (consumed by the next block's first GroupNorm)."""
+    if stats is not None:
+        t._cd360_gn_stats = (t._version, stats)
+    return t
+
+
+def _stats_of(t: torch.Tensor):
+    ent = getattr(t, "_cd360_gn_stats", None)
+    return ent[1] if ent is not None and ent[0] == t._version else None
+
+
+def _packed(mod: nn.Module, params, make):
+    """make() cached on mod, keyed on every parameter's (data_ptr, _version, dtype)."""
+    key = tuple((p.data_ptr(), p._version, p.dtype) for p in params if p is not None)
+    ent = mod.__dict__.get("_cd360_pack")
+    if ent is None or ent[0] != key:
+        ent = (key, make())
+        mod.__dict__["_cd360_pack"] = ent
+    return ent[1]
+
+
+def _gn(norm: nn.GroupNorm, rows: torch.Tensor, silu: bool, tile_stats=None, out=None) -> torch.Tensor:
+    return ops.gn_silu(rows, ops.bias_f32(norm.weight), ops.bias_f32(norm.bias), norm.num_groups, norm.eps, silu, out=out, tile_stats=tile_stats)
+
+
+def _conv_pack(conv: nn.Conv2d):
+    return ops.pack_conv_weight(conv.weight), ops.bias_f32(conv.bias).clone() if conv.bias is not None else None
+
+
+# ----------------------------------------------------------------------------------------------- blocks
+class Upsample(nn.Module):
+    def __init__(self, in_channels, with_conv):
+        super().__init__()
+        self.with_conv = with_conv
+        if self.with_conv:
+            self.conv = torch.nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1)
+
+    def forward(self, x):
+        if not self.with_conv:
+            raise NotImplementedError("Upsample(with_conv=False) is not used by the first stage (resamp_with_conv=True)")
+        _check_no_grad(self)
+        rows, n, c, h, w = _rows(x)
+        wph, b = _packed(self, (self.conv.weight, self.conv.bias),
+                         lambda: (ops.pack_upsample_conv_weight(self.conv.weight), ops.bias_f32(self.conv.bias).clone()))
+        return _nchw(ops.conv_up2x(rows, wph, b, n, h, w), n, 2 * h, 2 * w)
+
+
+class Downsample(nn.Module):
+    def __init__(self, in_channels, with_conv):
+        super().__init__()
+        self.with_conv = with_conv
+        if self.with_conv:
+            # no asymmetric padding in torch conv, must do it ourselves
+            self.conv = torch.nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=2, padding=0)
+
+    def forward(self, x):
+        raise NotImplementedError("Downsample belongs to Encoder.forward (encode_first_stage), which this package does not serve")
+
+
+class ResnetBlock(nn.Module):
+    def __init__(self, *, in_channels, out_channels=None, conv_shortcut=False, dropout, temb_channels=512):
+        super().__init__()
+        self.in_channels = in_channels
+        out_channels = in_channels if out_channels is None else out_channels
+        self.out_channels = out_channels
+        self.use_conv_shortcut = conv_shortcut
+
+        self.norm1 = Normalize(in_channels)
+        self.conv1 = torch.nn.Conv2d(in_channels, out_channels, kernel_size=3, stride=1, padding=1)
+        if temb_channels > 0:
+            self.temb_proj = torch.nn.Linear(temb_channels, out_channels)
+        self.norm2 = Normalize(out_channels)
+        self.dropout = torch.nn.Dropout(dropout)
+        self.conv2 = torch.nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1)
+        if self.in_channels != self.out_channels:
+            if self.use_conv_shortcut:
+                self.conv_shortcut = torch.nn.Conv2d(in_channels, out_channels, kernel_size=3, stride=1, padding=1)
+            else:
+                self.nin_shortcut = torch.nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=1, padding=0)
+
+    def _shortcut(self):
+        if self.in_channels == self.out_channels:
+            return None
+        return self.conv_shortcut if self.use_conv_shortcut else self.nin_shortcut
+
+    def forward(self, x, temb=None, **kwargs):
+        if temb is not None:
+            raise NotImplementedError("ResnetBlock with a time embedding (Model); the first stage passes temb=None")
+        if self.training and self.dropout.p > 0:
+            raise NotImplementedError("ResnetBlock dropout > 0 in train mode (the first stage's config has dropout 0)")
+        _check_no_grad(self)
+        rows, n, c, h, w = _rows(x)
+        sc = self._shortcut()
+        convs = (self.conv1, self.conv2) + ((sc,) if sc is not None else ())
+        packs = _packed(self, [p for m in convs for p in (m.weight, m.bias)], lambda: [_conv_pack(m) for m in convs])
+        hid = _gn(self.norm1, rows, True, tile_stats=_stats_of(x))
+        if (h * w) % 128 == 0:
+            hid, st = ops.conv_igemm(hid, packs[0][0], packs[0][1], n, h, w, 9, want_stats=True)
+        else:
+            hid, st = ops.conv_igemm(hid, packs[0][0], packs[0][1], n, h, w, 9), None
+        hid = _gn(self.norm2, hid, True, tile_stats=st, out=hid)
+        skip = rows
+        if sc is not None:
+            skip = ops.conv_igemm(rows, packs[2][0], packs[2][1], n, h, w, 1 if sc.kernel_size == (1, 1) else 9)
+        return _nchw(ops.conv_igemm(hid, packs[1][0], packs[1][1], n, h, w, 9, res=skip), n, h, w)
+
+
+class _SingleHeadAttn(nn.Module):
+    """AttnBlock / MemoryEfficientAttnBlock: the same arithmetic (single-head softmax(q k^T / sqrt(C)) v over all pixels) and kernels."""
+
+    def __init__(self, in_channels):
+        super().__init__()
+        self.in_channels = in_channels
+
+        self.norm = Normalize(in_channels)
+        self.q = torch.nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
+        self.k = torch.nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
+        self.v = torch.nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
+        self.proj_out = torch.nn.Conv2d(in_channels, in_channels, kernel_size=1, stride=1, padding=0)
+
+    def _pack(self):
+        def make():
+            wqkv, bqkv = ops.pack_attn_qkv(self.q.weight, self.q.bias, self.k.weight, self.k.bias, self.v.weight, self.v.bias)
+            return wqkv, bqkv, self.proj_out.weight.detach().reshape(self.in_channels, -1).to(torch.bfloat16).contiguous(), \
+                ops.bias_f32(self.proj_out.bias).clone()
+        return _packed(self, [p for m in (self.q, self.k, self.v, self.proj_out) for p in (m.weight, m.bias)], make)
+
+    def forward(self, x, **kwargs):
+        _check_no_grad(self)
+        rows, n, c, h, w = _rows(x)
+        wqkv, bqkv, wp, bp = self._pack()
+        hid = _gn(self.norm, rows, False)
+        qkv = ops.conv_igemm(hid, wqkv, bqkv, n, h, w, 1)  # [n, h w, 3 c]
+        att = ops.attention_single(qkv[..., :c], qkv[..., c:2 * c], qkv[..., 2 * c:])
+        return _nchw(ops.conv_igemm(att, wp, bp, n, h, w, 1, res=rows), n, h, w)
+
+
+class AttnBlock(_SingleHeadAttn):
+    pass
+
+
+class MemoryEfficientAttnBlock(_SingleHeadAttn):
+    """The reference's xformers block (model.py:204-265); here the same kernels as AttnBlock."""
+
+    def __init__(self, in_channels):
+        super().__init__(in_channels)
+        self.attention_op = None
+
+
+def make_attn(in_channels, attn_type="vanilla", attn_kwargs=None):
+    assert attn_type in ["vanilla", "vanilla-xformers", "memory-efficient-cross-attn", "linear", "none"], f"attn_type {attn_type} unknown"
+    if attn_type == "vanilla":
+        assert attn_kwargs is None
+        return AttnBlock(in_channels)
+    if attn_type == "vanilla-xformers":
+        return MemoryEfficientAttnBlock(in_channels)
+    if attn_type == "none":
+        return nn.Identity(in_channels)
+    raise NotImplementedError(f"attn_type {attn_type!r} is not used by the first stage's config (vanilla-xformers); not implemented")
+
+
+# ----------------------------------------------------------------------------------------------- encoder / decoder
+class Encoder(nn.Module):
+    def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0.0, resamp_with_conv=True,
+                 in_channels, resolution, z_channels, double_z=True, use_linear_attn=False, attn_type="vanilla", **ignore_kwargs):
+        super().__init__()
+        if use_linear_attn:
+            attn_type = "linear"
+        self.ch = ch
+        self.temb_ch = 0
+        self.num_resolutions = len(ch_mult)
+        self.num_res_blocks = num_res_blocks
+        self.resolution = resolution
+        self.in_channels = in_channels
+
+        self.conv_in = torch.nn.Conv2d(in_channels, self.ch, kernel_size=3, stride=1, padding=1)
+
+        curr_res = resolution
+        in_ch_mult = (1,) + tuple(ch_mult)
+        self.in_ch_mult = in_ch_mult
+        self.down = nn.ModuleList()
+        for i_level in range(self.num_resolutions):
+            block = nn.ModuleList()
+            attn = nn.ModuleList()
+            block_in = ch * in_ch_mult[i_level]
+            block_out = ch * ch_mult[i_level]
+            for i_block in range(self.num_res_blocks):
+                block.append(ResnetBlock(in_channels=block_in, out_channels=block_out, temb_channels=self.temb_ch, dropout=dropout))
+                block_in = block_out
+                if curr_res in attn_resolutions:
+                    attn.append(make_attn(block_in, attn_type=attn_type))
+            down = nn.Module()
+            down.block = block
+            down.attn = attn
+            if i_level != self.num_resolutions - 1:
+                down.downsample = Downsample(block_in, resamp_with_conv)
+                curr_res = curr_res // 2
+            self.down.append(down)
+
+        self.mid = nn.Module()
+        self.mid.block_1 = ResnetBlock(in_channels=block_in, out_channels=block_in, temb_channels=self.temb_ch, dropout=dropout)
+        self.mid.attn_1 = make_attn(block_in, attn_type=attn_type)
+        self.mid.block_2 = ResnetBlock(in_channels=block_in, out_channels=block_in, temb_channels=self.temb_ch, dropout=dropout)
+
+        self.norm_out = Normalize(block_in)
+        self.conv_out = torch.nn.Conv2d(block_in, 2 * z_channels if double_z else z_channels, kernel_size=3, stride=1, padding=1)
+
+    def forward(self, x):
+        raise NotImplementedError("Encoder.forward (encode_first_stage, training only) is not implemented on HIP")
+
+
+class Decoder(nn.Module):
+    def __init__(self, *, ch, out_ch, ch_mult=(1, 2, 4, 8), num_res_blocks, attn_resolutions, dropout=0.0, resamp_with_conv=True,
+                 in_channels, resolution, z_channels, give_pre_end=False, tanh_out=False, use_linear_attn=False, attn_type="vanilla",
+                 **ignorekwargs):
+        super().__init__()
+        if use_linear_attn:
+            attn_type = "linear"
+        self.ch = ch
+        self.temb_ch = 0
+        self.num_resolutions = len(ch_mult)
+        self.num_res_blocks = num_res_blocks
+        self.resolution = resolution
+        self.in_channels = in_channels
+        self.give_pre_end = give_pre_end
+        self.tanh_out = tanh_out
+
+        block_in = ch * ch_mult[self.num_resolutions - 1]
+        curr_res = resolution // 2 ** (self.num_resolutions - 1)
+        self.z_shape = (1, z_channels, curr_res, curr_res)
+
+        make_attn_cls = self._make_attn()
+        make_resblock_cls = self._make_resblock()
+        make_conv_cls = self._make_conv()
+        self.conv_in = torch.nn.Conv2d(z_channels, block_in, kernel_size=3, stride=1, padding=1)
+
+        self.mid = nn.Module()
+        self.mid.block_1 = make_resblock_cls(in_channels=block_in, out_channels=block_in, temb_channels=self.temb_ch, dropout=dropout)
+        self.mid.attn_1 = make_attn_cls(block_in, attn_type=attn_type)
+        self.mid.block_2 = make_resblock_cls(in_channels=block_in, out_channels=block_in, temb_channels=self.temb_ch, dropout=dropout)
+
+        self.up = nn.ModuleList()
+        for i_level in reversed(range(self.num_resolutions)):
+            block = nn.ModuleList()
+            attn = nn.ModuleList()
+            block_out = ch * ch_mult[i_level]
+            for i_block in range(self.num_res_blocks + 1):
+                block.append(make_resblock_cls(in_channels=block_in, out_channels=block_out, temb_channels=self.temb_ch, dropout=dropout))
+                block_in = block_out
+                if curr_res in attn_resolutions:
+                    attn.append(make_attn_cls(block_in, attn_type=attn_type))
+            up = nn.Module()
+            up.block = block
+            up.attn = attn
+            if i_level != 0:
+                up.upsample = Upsample(block_in, resamp_with_conv)
+                curr_res = curr_res * 2
+            self.up.insert(0, up)  # prepend to get consistent order
+
+        self.norm_out = Normalize(block_in)
+        self.conv_out = make_conv_cls(block_in, out_ch, kernel_size=3, stride=1, padding=1)
+
+    def _make_attn(self):
+        return make_attn
+
+    def _make_resblock(self):
+        return ResnetBlock
+
+    def _make_conv(self):
+        return torch.nn.Conv2d
+
+    def get_last_layer(self, **kwargs):
+        return self.conv_out.weight
+
+    def max_batch(self, h: int, w: int) -> int:
+        """Images of an h x w latent that could share one pass: every activation the convolution cores read (and every q|k|v
+        projection / Upsample output they write) stays below 2^31 bytes.  forward() decodes one image per pass (see there)."""
+        hw, biggest = h * w, 0
+        c = self.conv_in.out_channels
+
+        def see(pixels, channels):
+            nonlocal biggest
+            biggest = max(biggest, pixels * channels * 2)
+
+        see(hw, c)
+        see(hw, 3 * c)  # mid.attn_1's q|k|v
+        for i_level in reversed(range(self.num_resolutions)):
+            up = self.up[i_level]
+            for i_block, blk in enumerate(up.block):
+                see(hw, blk.in_channels)
+                see(hw, blk.out_channels)
+                if len(up.attn) > 0:
+                    see(hw, 3 * blk.out_channels)
+            if i_level != 0:
+                hw *= 4
+                see(hw, up.upsample.conv.out_channels)
+        return max(1, (_INT32_BYTES - 1) // biggest)
+
+    def forward(self, z, **kwargs):
+        self.last_z_shape = z.shape
+        if self.give_pre_end or self.tanh_out:
+            raise NotImplementedError("Decoder(give_pre_end=True | tanh_out=True) is not used by the first stage; not implemented")
+        _check_no_grad(self)
+        if not z.is_cuda:
+            raise ops.Cd360Error("the first-stage HIP modules run only on the GPU; got a CPU tensor")
+        # one image per pass: an image decodes to the same bits in a batch of any size.  A batch-folded pass (_decode_pass on the whole
+        # batch, legal up to max_batch(h, w) images) lets the convolution cores pick their tiling from the batch's pixel count, which
+        # changes fp32 summation orders and so the bf16 roundings downstream; at a 1024^2 image one image already fills the chip
+        if z.shape[0] == 1:
+            return self._decode_pass(z, **kwargs)
+        return torch.cat([self._decode_pass(z[i:i + 1], **kwargs) for i in range(z.shape[0])], 0)
+
+    def _decode_pass(self, z, **kwargs):
+        """One pass of the decoder over the whole batch z (at most max_batch(h, w) images)."""
+        n, cz, h, w = z.shape
+        if n > self.max_batch(h, w):
+            raise ops.Cd360Error(f"{n} images of {h} x {w} exceed the 32-bit offsets of the convolution cores in one pass")
+        temb = None
+
+        win, bin_, wout, bout = _packed(self, (self.conv_in.weight, self.conv_in.bias, self.conv_out.weight, self.conv_out.bias), lambda: (
+            ops.pack_vae_conv_in_weight(self.conv_in.weight), ops.bias_f32(self.conv_in.bias).clone(),
+            ops.pack_vae_conv_out_weight(self.conv_out.weight), ops.bias_f32(self.conv_out.bias).clone()))
+        z32 = z.float().contiguous()
+        if (h * w) % 64 == 0:
+            rows, st = ops.vae_conv_in(z32, win, bin_, want_stats=True)
+        else:
+            rows, st = ops.vae_conv_in(z32, win, bin_), None
+        hid = _with_stats(_nchw(rows, n, h, w), st)
+
+        hid = self.mid.block_1(hid, temb, **kwargs)
+        hid = self.mid.attn_1(hid, **kwargs)
+        hid = self.mid.block_2(hid, temb, **kwargs)
+
+        for i_level in reversed(range(self.num_resolutions)):
+            for i_block in range(self.num_res_blocks + 1):
+                hid = self.up[i_level].block[i_block](hid, temb, **kwargs)
+                if len(self.up[i_level].attn) > 0:
+                    hid = self.up[i_level].attn[i_block](hid, **kwargs)
+            if i_level != 0:
+                hid = self.up[i_level].upsample(hid)
+
+        rows, n, c, hh, ww = _rows(hid)
+        act = _gn(self.norm_out, rows, True)
+        out = ops.vae_conv_out(act, wout, bout, n, hh, ww, self.conv_out.out_channels)
+        return out.to(self.conv_out.weight.dtype)

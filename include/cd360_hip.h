@@ -137,6 +137,33 @@ int cd360_attn_bwd_bf16(const void* q, const void* k, const void* v, const void*
 /* xformers layout: q, k, v, o contiguous [B*H, N, 64], exactly the call of attention.py:406. */
 int cd360_attn_fwd_xformers_bf16(const void* q, const void* k, const void* v, void* o, int BH, int Nq, int Nk, float scale, void* stream);
 
+/* ---- the first-stage decoder (AutoencoderKL.decode -> Decoder.forward, sgm/modules/diffusionmodules/model.py:604-733) ----------------
+ * replaces xformers.ops.memory_efficient_attention(q, k, v) of MemoryEfficientAttnBlock.attention (model.py:204-265) and the full score
+ * matrix of AttnBlock.attention (:161-201): ONE head, head dim D = C (D % 64 == 0, 64 <= D <= 512), Nq = Nk = N >= 1 (a ragged last key
+ * tile is masked).  q, k, v [B, N, D] bf16 at b * strides[0] + n * strides[1] + d (element strides, multiples of 8; 16-byte aligned):
+ * e.g. the three column slices of one merged q|k|v projection [B * N, 3 D]; o likewise (strides multiples of 4, 8-byte aligned).
+ * o = softmax_2(qscale * q k^T) v with fp32 running maximum, sum and accumulator: prescaled callers fold C^-0.5 * log2 e into the q rows of
+ * the packed projection and pass qscale = 1 (the convention of cd360_attn_fwd_prescaled_bf16); qscale = D^-0.5 * log2 e serves plain q.
+ * The N x N matrix never reaches memory.  Keys are split over cd360_attn_single_splits(B, N) (a function of N alone) workgroups per 64-query block (partial O and
+ * log-sum-exp in ws, merged by a second kernel); ws = cd360_attn_single_workspace_bytes(B, N, D) bytes (0: no split, ws may be NULL). */
+int cd360_attn_single_splits(int B, int N);
+int64_t cd360_attn_single_workspace_bytes(int B, int N, int D);
+int cd360_attn_single_bf16(const void* q, const void* k, const void* v, void* o, int B, int N, int D, const int64_t* q_strides,
+                           const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, float qscale, void* ws, void* stream);
+/* replaces Decoder.conv_in (model.py:651-654, applied at :721): Conv2d(z_channels -> Cout, 3 x 3, padding 1) on the sampler's latent.
+ * z fp32 NCHW [B, Cz, H, W], Cz <= 8; w fp32 [Cz * 9, Cout] (row ci * 9 + 3 ky + kx = weight[:, ci, ky, kx]); bias fp32 [Cout] | NULL
+ * -> out bf16 channels-last [B, H W, Cout].  Cout % 64 == 0, Cout <= 1024.  tile_stats (optional, NULL to skip; requires H W % 64 == 0): fp32
+ * [B, cd360_vae_conv_in_stats_slabs(H, W), Cout, 2] channel sums / sums of squares of the bf16 outputs per 64-pixel slab, for the
+ * cd360_gn_silu_bf16 of mid.block_1.norm1. */
+int cd360_vae_conv_in_stats_slabs(int H, int W);
+int cd360_vae_conv_in_f32(const void* z, const void* w, const void* bias, void* out, void* tile_stats, int B, int Cz, int H, int W, int Cout,
+                          void* stream);
+/* replaces Decoder.conv_out (model.py:699-701, applied at :731-733 behind norm_out + nonlinearity): Conv2d(Cin -> Cout, 3 x 3, padding 1)
+ * writing the tensor Decoder.forward returns.  x bf16 channels-last [B, H W, Cin] (after GroupNorm + SiLU), Cin % 64 == 0; w fp32
+ * [9, Cin, 4] (tap 3 ky + kx, channel, output channel; columns >= Cout zero); bias fp32 [Cout] | NULL -> out fp32 NCHW [B, Cout, H, W].
+ * Cout <= 4, any H and W. */
+int cd360_vae_conv_out_bf16(const void* x, const void* w, const void* bias, void* out, int B, int H, int W, int Cin, int Cout, void* stream);
+
 /* ---- rays, projection, integer bilinear indices ----------------------------------------------------------------
  * replaces get_patch_rays / get_patch_raybundle / get_directional_raybundle  (sgm/modules/utils_cameraray.py:61-196)
  *          and the pytorch3d calls inside them (unproject_points, get_camera_center).
