@@ -4,7 +4,7 @@ No operator here has a PyTorch/CPU implementation: a CPU tensor (or a missing li
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -735,6 +735,46 @@ def conv_igemm(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Ten
         check(lib.cd360_conv_igemm_bf16(_ptr(x), _ptr(w_packed), _ptr(bias), _ptr(emb), 0 if emb is None else emb.stride(0), _ptr(res), _ptr(out),
                                        N, H, W, cin, cout, taps, stride, _ptr(stats), _stream()), "cd360_conv_igemm_bf16")
     return (out, stats) if want_stats else out
+
+
+class ConvRoute(NamedTuple):
+    """The kernel a convolution launch runs (cd360_conv_route): family "register" (the register-staged kernel), "dma" (the LDS-DMA
+    core: `tiling` 1..6, `halo` = the halo form, `slab_rows` = pixels per tile_stats slab) or "gemm" (1 x 1 on cd360_gemm_bf16)."""
+    family: str
+    tiling: int
+    halo: bool
+    slab_rows: int
+
+
+_ROUTE_TILING_MASK, _ROUTE_HALO, _ROUTE_GEMM, _ROUTE_SLAB_SHIFT = 15, 16, 32, 8  # include/cd360_hip.h: CD360_ROUTE_*
+
+
+def decode_conv_route(route: int) -> ConvRoute:
+    if route == _ROUTE_GEMM:
+        return ConvRoute("gemm", 0, False, 0)
+    if route == 0:
+        return ConvRoute("register", 0, False, 0)
+    return ConvRoute("dma", route & _ROUTE_TILING_MASK, bool(route & _ROUTE_HALO), route >> _ROUTE_SLAB_SHIFT)
+
+
+def conv_route(N: int, H: int, W: int, cin: int, cout: int, taps: int = 9, stride: int = 1) -> ConvRoute:
+    """What conv_igemm launches for this shape on the current stream (its per-stream tuning included)."""
+    _lib.query_stream(_stream())
+    return decode_conv_route(_lib.load().cd360_conv_route(N, H, W, cin, cout, taps, stride))
+
+
+def conv3x3_dma_route(N: int, H: int, W: int, cin: int, cout: int) -> ConvRoute:
+    """What cd360_conv3x3_dma_bf16 itself launches for this shape on the current stream (family "register": outside its envelope)."""
+    _lib.query_stream(_stream())
+    return decode_conv_route(_lib.load().cd360_conv3x3_dma_route(N, H, W, cin, cout))
+
+
+def conv_up2x_tiling(N: int, H: int, W: int, cin: int, cout: int) -> int:
+    """The tiling (1..6) conv_up2x launches for this source image on the current stream."""
+    _lib.query_stream(_stream())
+    t = _lib.load().cd360_conv_up2x_route(N, H, W, cin, cout)
+    check(min(t, 0), "cd360_conv_up2x_route")
+    return t
 
 
 def pack_upsample_conv_weight(w: torch.Tensor) -> torch.Tensor:

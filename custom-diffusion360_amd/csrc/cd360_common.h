@@ -17,6 +17,12 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 #define CD360_ERR_SHAPE (-2)
 #define CD360_ERR_LAUNCH (-3)
 
+// cd360_conv_route encoding (include/cd360_hip.h): tiling in bits 0-3, flags, slab rows from bit 8
+#define CD360_ROUTE_TILING_MASK 15
+#define CD360_ROUTE_HALO 16
+#define CD360_ROUTE_GEMM 32
+#define CD360_ROUTE_SLAB_SHIFT 8
+
 #define CD360_LAUNCH_CHECK()                                   \
   do {                                                         \
     hipError_t e__ = hipGetLastError();                        \

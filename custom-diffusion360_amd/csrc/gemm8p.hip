@@ -1556,14 +1556,16 @@ int launch_epi(const GemmParams& p, hipStream_t stream) {
 // the 1280-level shapes, interleaved on one box (tools/bench_gemm.py ksplit, us, mode 0 / mode 1): K = 1280 19.9 / 20.7, K = 2560
 // 30.0 / 29.7, K = 5120 51.9 / 49.3, the 3 x 3 convolutions at 32^2 (K = 11520 .. 23040) 112.7 / 108.4, 166.5 / 156.5, 220.0 / 206.0 --
 // so the split serves K >= 3072.  (Mode 2, four waves of 64 x 64 with one wave per SIMD, is 10 % slower everywhere: kept for A/B only.)
-// cd360_tuning.gemm_ksplit = 0 | 1 | 2 forces a mode.
+// cd360_tuning.gemm_ksplit = 0 | 1 | 2 forces a mode.  Every mode has the same NMB: the statistics slabs (NMB * 32 pixels) of the
+// 128 x 128 convolution tiling and of the halo form do not depend on the mode.
+constexpr int NMB_128X4 = 2;
 template <int EPI>
 int launch_128x4(const GemmParams& p, hipStream_t stream) {
   const int forced = cd360_tune().gemm_ksplit;
   const int mode = forced >= 0 ? forced : (p.K >= 3072 ? 1 : 0);
-  if (mode == 1) return launch_ks<2, 2, 2, 2, 4, 2, EPI>(p, stream);
-  if (mode == 2) return launch_ks<2, 2, 2, 2, 4, 1, EPI>(p, stream);
-  return launch_ks<2, 4, 1, 2, 4, 1, EPI>(p, stream);
+  if (mode == 1) return launch_ks<2, 2, 2, NMB_128X4, 4, 2, EPI>(p, stream);
+  if (mode == 2) return launch_ks<2, 2, 2, NMB_128X4, 4, 1, EPI>(p, stream);
+  return launch_ks<2, 4, 1, NMB_128X4, 4, 1, EPI>(p, stream);
 }
 
 // 64 x 128 tiles for launches whose 128 x 128 tiling would leave more than half of the 256 CUs without a workgroup (the 1280-wide
@@ -1939,9 +1941,10 @@ namespace {
 // 5 = 192 x 320 (round 5; six waves of 64 x 160): the 320-channel convolutions at 128^2, M = 49152 = 256 tiles of 192 -- one per CU, where
 // tiling 1 leaves a quarter of the CUs without a workgroup (192 tiles)
 // (six waves put two on two SIMDs and one on the others); 6 = the same tile as twelve waves of 32 x 160 (three per SIMD)
+// CONV_NMB: 32-pixel blocks per wave (the NMB template argument launch_conv passes), so a tile_stats slab is CONV_NMB * 32 pixels
 constexpr int NCONV = 6;
 constexpr int CONV_BM[NCONV + 1] = {0, 256, 256, 256, 128, 192, 192}, CONV_BN[NCONV + 1] = {0, 320, 128, 256, 128, 320, 320},
-              CONV_SLAB[NCONV + 1] = {0, 64, 64, 128, 64, 64, 32};
+              CONV_NMB[NCONV + 1] = {0, 2, 2, 4, NMB_128X4, 2, 1};
 int pick_conv_cfg(long M, int Cout) {
   {
     const int c = cd360_tune().conv_cfg;
@@ -1979,19 +1982,74 @@ bool conv_dma_ok(int N, int H, int W, int Cin, int Cout, int taps, int stride) {
   const long M = (long)N * H * W;
   return M * Cin * 2 < (1L << 31) && ((long)Cout + 320) * 9 * Cin * 2 < (1L << 32);
 }
+
+// The kernel cd360_conv3x3_dma_bf16 launches for this shape under cd360_tune(): its dispatch, its tile_stats check and every shape
+// query (cd360_conv_route, cd360_conv_dma_slab_rows, cd360_conv_stats_rows) read this one decision.
+struct ConvRoute {
+  int cfg;        // tiling 1 .. NCONV (pick_conv_cfg)
+  bool halo;      // the halo form (EPI 11 on launch_128x4) serves the call whatever the tiling
+  int slab_rows;  // pixels per tile_stats slab of the kernel that runs: NMB * 32
+};
+ConvRoute conv3x3_route(int N, int H, int W, int Cin, int Cout) {
+  ConvRoute r;
+  r.cfg = pick_conv_cfg((long)N * H * W, Cout);
+  r.halo = conv_halo_ok(N, H, W, Cin, Cout, r.cfg);
+  r.slab_rows = 32 * (r.halo ? NMB_128X4 : CONV_NMB[r.cfg]);
+  return r;
+}
+// the folded upsample (cd360_conv_up2x_bf16): the four phases share the launch, so the tile count is that of the full-resolution output
+int up2x_cfg(int N, int H, int W, int Cout) { return pick_conv_cfg(4L * N * H * W, Cout); }
+
+// the tap-shifted kernel (EPI 5) of tiling cfg; the template's NMB is CONV_NMB[cfg]
+int launch_conv(int cfg, const GemmParams& p, hipStream_t stream) {
+  switch (cfg) {
+    case 1: return launch_epi<4, 2, 5, CONV_NMB[1], 2, 5>(p, stream);
+    case 2: return launch_epi<4, 2, 2, CONV_NMB[2], 3, 5>(p, stream);
+    case 3: return launch_epi<2, 4, 2, CONV_NMB[3], 2, 5>(p, stream);
+    case 5: return launch_epi<3, 2, 5, CONV_NMB[5], 2, 5>(p, stream);
+    case 6: return launch_epi<6, 2, 5, CONV_NMB[6], 2, 5>(p, stream);
+    default: return launch_128x4<5>(p, stream);
+  }
+}
 }  // namespace
 
 extern "C" int cd360_conv_k_order(int Cin, int taps);
+extern "C" int cd360_conv3x3_dma_route(int N, int H, int W, int Cin, int Cout);
 
-// Pixels per slab of the `tile_stats` output of cd360_conv_igemm_bf16 for this convolution (the launch's wave tiling decides), or 0
-// when the call is served by the register-staged kernel (then 128 / cd360_conv_stats_slabs(Cout)).
-extern "C" int cd360_conv_dma_slab_rows(int N, int H, int W, int Cin, int Cout, int taps, int stride) {
-  if (!conv_dma_ok(N, H, W, Cin, Cout, taps, stride)) return 0;
-  const int rows = CONV_SLAB[pick_conv_cfg((long)N * H * W, Cout)];
-  return ((long)H * W) % rows ? 0 : rows;
+// Route of cd360_conv_igemm_bf16 for this convolution under the tuning the calling thread's launches read (see cd360_query_stream):
+// 0 = the register-staged kernel; else the LDS-DMA core, encoded as the tiling | CD360_ROUTE_HALO | slab rows << CD360_ROUTE_SLAB_SHIFT
+// (the 3 x 3 / stride 1 convolutions whose images are whole slabs), or CD360_ROUTE_GEMM (a 1 x 1 convolution through cd360_gemm_bf16,
+// taken when the call passes neither emb nor tile_stats).
+extern "C" int cd360_conv_route(int N, int H, int W, int Cin, int Cout, int taps, int stride) {
+  const int dma = taps == 9 && stride == 1 ? cd360_conv3x3_dma_route(N, H, W, Cin, Cout) : 0;
+  if (dma && ((long)H * W) % (dma >> CD360_ROUTE_SLAB_SHIFT) == 0) return dma;
+  if (taps == 1 && stride == 1 && N > 0 && H > 0 && W > 0 && Cin % 64 == 0 && Cout % 16 == 0 && cd360_tune().conv_dma != 0) return CD360_ROUTE_GEMM;
+  return 0;
 }
 
-// Same contract as cd360_conv_igemm_bf16 for taps = 9, stride = 1; tile_stats fp32 [N H W / cd360_conv_dma_slab_rows(...), Cout, 2].
+// Route of cd360_conv3x3_dma_bf16 itself (encoded as cd360_conv_route's LDS-DMA routes; it takes images that are not whole slabs when
+// it writes no statistics), or 0 outside its envelope
+extern "C" int cd360_conv3x3_dma_route(int N, int H, int W, int Cin, int Cout) {
+  if (!conv_dma_ok(N, H, W, Cin, Cout, 9, 1)) return 0;
+  const ConvRoute r = conv3x3_route(N, H, W, Cin, Cout);
+  return r.cfg | (r.halo ? CD360_ROUTE_HALO : 0) | (r.slab_rows << CD360_ROUTE_SLAB_SHIFT);
+}
+
+// Tiling of cd360_conv_up2x_bf16 for this source image (it writes no statistics), or CD360_ERR_SHAPE outside its envelope
+extern "C" int cd360_conv_up2x_route(int N, int H, int W, int Cin, int Cout) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cin % 64 || Cout % 16) return CD360_ERR_SHAPE;
+  return up2x_cfg(N, H, W, Cout);
+}
+
+// Pixels per slab of the `tile_stats` output of cd360_conv_igemm_bf16 for this convolution (the kernel that runs decides), or 0
+// when the call is served by the register-staged kernel (then 128 / cd360_conv_stats_slabs(Cout)).
+extern "C" int cd360_conv_dma_slab_rows(int N, int H, int W, int Cin, int Cout, int taps, int stride) {
+  const int route = cd360_conv_route(N, H, W, Cin, Cout, taps, stride);
+  return route >> CD360_ROUTE_SLAB_SHIFT;
+}
+
+// Same contract as cd360_conv_igemm_bf16 for taps = 9, stride = 1; tile_stats fp32 [N H W / slab rows, Cout, 2], with the slab rows
+// of conv3x3_route (what cd360_conv_dma_slab_rows reports whenever it is not 0).
 // CD360_ERR_SHAPE when the shape is outside the envelope (the caller then uses the register-staged kernel).
 extern "C" int cd360_conv3x3_dma_bf16(const void* x, const void* w_packed, const void* bias, const void* emb, int64_t emb_stride, const void* res,
                                       void* out, int N, int H, int W, int Cin, int Cout, void* tile_stats, void* stream) {
@@ -2001,8 +2059,8 @@ extern "C" int cd360_conv3x3_dma_bf16(const void* x, const void* w_packed, const
   if (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)out | (uintptr_t)emb | (uintptr_t)res | (uintptr_t)tile_stats) % 16 || (uintptr_t)bias % 8) return CD360_ERR_ARG;
   if (emb && (emb_stride < Cout || emb_stride % 8)) return CD360_ERR_SHAPE;
   const long M = (long)N * H * W;
-  const int cfg = pick_conv_cfg(M, Cout);
-  if (tile_stats && ((long)H * W) % CONV_SLAB[cfg]) return CD360_ERR_SHAPE;
+  const ConvRoute route = conv3x3_route(N, H, W, Cin, Cout);
+  if (tile_stats && ((long)H * W) % route.slab_rows) return CD360_ERR_SHAPE;
   GemmParams p;
   p.a = (const uint16_t*)x; p.w = (const uint16_t*)w_packed; p.out = (uint16_t*)out; p.bias = (const float*)bias; p.res = (const uint16_t*)res;
   p.ln_stats = nullptr; p.wsum = nullptr; p.stats_out = nullptr;
@@ -2012,15 +2070,8 @@ extern "C" int cd360_conv3x3_dma_bf16(const void* x, const void* w_packed, const
   p.ak = p.av = nullptr; p.ak_sb = p.ak_sn = p.av_sb = p.av_sn = 0; p.a_nq = p.a_nk = 0; p.a_scale_log2e = 0.f; p.a_dup = p.a_dup_from = 0; p.a_kv8 = nullptr; p.a_kvs = nullptr; p.a_heads = 0;
   p.cv_H = H; p.cv_W = W; p.cv_kg = cd360_conv_k_order(Cin, 9); p.cv_up = 0;
   p.emb = (const uint16_t*)emb; p.emb_stride = emb ? emb_stride : 0; p.cstats = (float*)tile_stats;
-  if (conv_halo_ok(N, H, W, Cin, Cout, cfg)) return launch_128x4<11>(p, (hipStream_t)stream);
-  switch (cfg) {
-    case 1: return launch_epi<4, 2, 5, 2, 2, 5>(p, (hipStream_t)stream);
-    case 2: return launch_epi<4, 2, 2, 2, 3, 5>(p, (hipStream_t)stream);
-    case 3: return launch_epi<2, 4, 2, 4, 2, 5>(p, (hipStream_t)stream);
-    case 5: return launch_epi<3, 2, 5, 2, 2, 5>(p, (hipStream_t)stream);
-    case 6: return launch_epi<6, 2, 5, 1, 2, 5>(p, (hipStream_t)stream);
-    default: return launch_128x4<5>(p, (hipStream_t)stream);
-  }
+  if (route.halo) return launch_128x4<11>(p, (hipStream_t)stream);
+  return launch_conv(route.cfg, p, (hipStream_t)stream);
 }
 
 // Upsample.forward (openaimodel.py:114-181): nearest-neighbour 2x interpolation followed by conv3x3 / pad 1, as ONE launch that never
@@ -2046,14 +2097,7 @@ extern "C" int cd360_conv_up2x_bf16(const void* x, const void* w_phases, const v
   p.ak = p.av = nullptr; p.ak_sb = p.ak_sn = p.av_sb = p.av_sn = 0; p.a_nq = p.a_nk = 0; p.a_scale_log2e = 0.f; p.a_dup = p.a_dup_from = 0; p.a_kv8 = nullptr; p.a_kvs = nullptr; p.a_heads = 0;
   p.cv_H = H; p.cv_W = W; p.cv_kg = cd360_conv_k_order(Cin, 9); p.cv_up = 1;
   p.emb = nullptr; p.emb_stride = 0; p.cstats = nullptr;
-  switch (pick_conv_cfg(4 * M, Cout)) {  // the four phases share the launch: tile count of the full-resolution output
-    case 1: return launch_epi<4, 2, 5, 2, 2, 5>(p, (hipStream_t)stream);
-    case 2: return launch_epi<4, 2, 2, 2, 3, 5>(p, (hipStream_t)stream);
-    case 3: return launch_epi<2, 4, 2, 4, 2, 5>(p, (hipStream_t)stream);
-    case 5: return launch_epi<3, 2, 5, 2, 2, 5>(p, (hipStream_t)stream);
-    case 6: return launch_epi<6, 2, 5, 1, 2, 5>(p, (hipStream_t)stream);
-    default: return launch_128x4<5>(p, (hipStream_t)stream);
-  }
+  return launch_conv(up2x_cfg(N, H, W, Cout), p, (hipStream_t)stream);
 }
 
 // Per-row (sum, sumsq) of a bf16 [rows, C] matrix (row stride ld) as ONE partial per row: the `ln_stats` input of cd360_gemm_bf16 for a

@@ -126,8 +126,9 @@ extern "C" int cd360_get_stream_tuning(void* stream, cd360_tuning* t) {
 }
 
 // The shape queries (cd360_gemm_tile_n, cd360_gemm_cstats_rows, cd360_conv_stats_slabs, cd360_conv_stats_rows, cd360_conv_dma_slab_rows,
-// cd360_conv_k_order) size buffers for a launch that follows and take no stream: on the CALLING THREAD they answer for the stream named
-// by the last cd360_query_stream (NULL, or a stream without an override: the default).  Thread-local; nothing shared is written.
+// cd360_conv_route, cd360_conv3x3_dma_route, cd360_conv_up2x_route, cd360_conv_k_order) size buffers for a launch that follows and take
+// no stream: on the CALLING THREAD they answer for the stream named by the last cd360_query_stream (NULL, or a stream without an
+// override: the default).  Thread-local; nothing shared is written.
 extern "C" int cd360_query_stream(void* stream) {
   if (stream && g_nstreams.load(std::memory_order_relaxed) != 0 && lookup(stream, &tl_query)) tl_tune = &tl_query;
   else tl_tune = nullptr;

@@ -69,8 +69,9 @@ int cd360_get_tuning(cd360_tuning* t);
  * issued ON `stream` reads *t instead of the default, so two samplers / two captures in one process hold different tilings; t == NULL
  * removes the override; at most 16 streams; thread-safe.  cd360_get_stream_tuning returns what launches on `stream` read (override or
  * default).  The shape queries below that size a buffer for a following launch (cd360_gemm_tile_n, cd360_gemm_cstats_rows,
- * cd360_conv_stats_slabs, cd360_conv_stats_rows, cd360_conv_dma_slab_rows, cd360_conv_k_order) take no stream: on the CALLING THREAD they
- * answer for the stream named by the last cd360_query_stream (NULL or a stream without override: the default) -- thread-local state only. */
+ * cd360_conv_stats_slabs, cd360_conv_stats_rows, cd360_conv_dma_slab_rows, cd360_conv_route, cd360_conv3x3_dma_route, cd360_conv_up2x_route,
+ * cd360_conv_k_order) take no stream: on the CALLING THREAD they answer for the stream named by the last cd360_query_stream (NULL or a
+ * stream without override: the default) -- thread-local state only. */
 int cd360_set_stream_tuning(void* stream, const cd360_tuning* t);
 int cd360_get_stream_tuning(void* stream, cd360_tuning* t);
 int cd360_query_stream(void* stream);
@@ -400,6 +401,25 @@ int cd360_conv_stats_rows(int N, int H, int W, int Cin, int Cout, int taps, int 
  * buffer descriptor's range check); cd360_conv_igemm_bf16 forwards to it whenever cd360_conv_dma_slab_rows(...) > 0.
  * tile_stats fp32 [N*H*W / cd360_conv_dma_slab_rows(...), Cout, 2]. */
 int cd360_conv_dma_slab_rows(int N, int H, int W, int Cin, int Cout, int taps, int stride);
+/* The kernel cd360_conv_igemm_bf16 runs for this convolution: 0 = the register-staged kernel; otherwise the LDS-DMA core, as
+ *   route & CD360_ROUTE_TILING_MASK   tiling 1..6 of cd360_tuning.conv_cfg (a forced tiling that the shape cannot take -- 1, 5, 6 need
+ *                                     Cout % 320 == 0 -- is replaced by the measured default)
+ *   route & CD360_ROUTE_HALO          the halo form serves the call, whatever the tiling
+ *   route >> CD360_ROUTE_SLAB_SHIFT   pixels per tile_stats slab of the kernel that runs (32 * its NMB: 32, 64 or 128; 64 for the halo
+ *                                     form) = cd360_conv_dma_slab_rows
+ * or route == CD360_ROUTE_GEMM: a 1 x 1 convolution on the GEMM entry, cd360_gemm_bf16; calls with emb or tile_stats take the
+ * register-staged kernel.
+ * cd360_conv_dma_slab_rows, cd360_conv_stats_rows and the launch itself read the same decision, so a buffer sized from them fits. */
+#define CD360_ROUTE_TILING_MASK 15
+#define CD360_ROUTE_HALO 16
+#define CD360_ROUTE_GEMM 32
+#define CD360_ROUTE_SLAB_SHIFT 8
+int cd360_conv_route(int N, int H, int W, int Cin, int Cout, int taps, int stride);
+/* The route of cd360_conv3x3_dma_bf16 itself, encoded as above (it also serves images that are not whole slabs, without tile_stats),
+ * or 0 outside its envelope. */
+int cd360_conv3x3_dma_route(int N, int H, int W, int Cin, int Cout);
+/* Tiling (1..6, as above) of cd360_conv_up2x_bf16 for the source image N x H x W, or CD360_ERR_SHAPE outside its envelope. */
+int cd360_conv_up2x_route(int N, int H, int W, int Cin, int Cout);
 int cd360_conv3x3_dma_bf16(const void* x, const void* w_packed, const void* bias, const void* emb, int64_t emb_stride, const void* res,
                            void* out, int N, int H, int W, int Cin, int Cout, void* tile_stats, void* stream);
 
