@@ -30,6 +30,9 @@ SIGNATURES = {
     "cd360_vae_conv_in_stats_slabs": (c_int, [c_int, c_int]),
     "cd360_vae_conv_in_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "cd360_vae_conv_out_bf16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "cd360_vae_downsample_stats_rows": (c_int, [c_int, c_int, c_int, c_int]),
+    "cd360_vae_downsample_bf16": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "cd360_vae_enc_conv_out_bf16": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "cd360_patch_rays": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "cd360_ray_project_index": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "cd360_sample_pdf": (c_int, [_P, _P, _P, _P, _P, c_float, c_int64, c_int, c_int, _P]),

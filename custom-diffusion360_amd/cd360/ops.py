@@ -1336,6 +1336,60 @@ def vae_conv_out(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.T
     return out
 
 
+# ----------------------------------------------------------------------------------------------- the first stage's encoder
+def vae_downsample_stats_rows(N: int, H: int, W: int, C: int) -> int:
+    """Pixels per tile_stats slab of vae_downsample for this shape on the current stream (0: the output has no slabs)."""
+    _lib.query_stream(_stream())
+    return _lib.load().cd360_vae_downsample_stats_rows(N, H, W, C)
+
+
+def vae_downsample(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], N: int, H: int, W: int, want_stats: bool = True):
+    """Encoder Downsample (with_conv=True): x bf16 channels-last [N, H W, C], w_packed = pack_conv_weight(conv.weight) -> (out bf16
+    [N, (H // 2) (W // 2), C], tile_stats) = conv3x3 / stride 2 of F.pad(x, (0, 1, 0, 1)) (cd360_vae_downsample_bf16).  tile_stats: fp32
+    [N, slabs, C, 2] for gn_silu(out, ..., tile_stats=tile_stats) when want_stats and the shape has slabs
+    (cd360_vae_downsample_stats_rows), else None."""
+    _need_gpu(x, w_packed, bias)
+    c = x.shape[-1]
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and x.numel() == N * H * W * c
+    assert w_packed.dtype == torch.bfloat16 and w_packed.is_contiguous() and w_packed.shape == (c, 9 * c)
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == c)
+    ho, wo = H // 2, W // 2
+    lib = _lib.load()
+    out = torch.empty(N, ho * wo, c, dtype=torch.bfloat16, device=x.device)
+    rows = vae_downsample_stats_rows(N, H, W, c) if want_stats else 0
+    stats = torch.empty(N, (ho * wo) // rows, c, 2, dtype=torch.float32, device=x.device) if rows > 0 else None
+    m = N * ho * wo
+    with _timed("vae_downsample", 2.0 * m * 9 * c * c, 2.0 * (N * H * W * c + m * c + 9 * c * c)):
+        check(lib.cd360_vae_downsample_bf16(_ptr(x), _ptr(w_packed), _ptr(bias), _ptr(out), _ptr(stats), N, H, W, c, _stream()),
+              "cd360_vae_downsample_bf16")
+    return out, stats
+
+
+def pack_vae_enc_conv_out_weight(w: torch.Tensor) -> torch.Tensor:
+    """Encoder.conv_out weight [Cout <= 8, Cin, 3, 3] -> fp32 [9, Cin, 8] (tap 3 ky + kx, channel, output channel; columns >= Cout zero)
+    (cd360_vae_enc_conv_out_bf16)."""
+    cout, cin, kh, kw = w.shape
+    assert kh == 3 and kw == 3 and cout <= 8
+    out = torch.zeros(9, cin, 8, dtype=torch.float32, device=w.device)
+    out[:, :, :cout] = w.detach().float().permute(2, 3, 1, 0).reshape(9, cin, cout)
+    return out
+
+
+def vae_enc_conv_out(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], N: int, H: int, W: int, cout: int) -> torch.Tensor:
+    """Encoder.conv_out: x bf16 channels-last [N, H W, Cin] (after norm_out + SiLU) -> fp32 NCHW [N, cout, H, W]
+    (cd360_vae_enc_conv_out_bf16)."""
+    _need_gpu(x, w_packed, bias)
+    cin = x.shape[-1]
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and x.numel() == N * H * W * cin and 1 <= cout <= 8
+    assert w_packed.dtype == torch.float32 and w_packed.is_contiguous() and w_packed.shape == (9, cin, 8)
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == cout)
+    out = torch.empty(N, cout, H, W, dtype=torch.float32, device=x.device)
+    with _timed("vae_enc_conv_out", 2.0 * N * H * W * 9 * cin * cout, 2.0 * N * H * W * cin + 4.0 * N * H * W * cout):
+        check(_lib.load().cd360_vae_enc_conv_out_bf16(_ptr(x), _ptr(w_packed), _ptr(bias), _ptr(out), N, H, W, cin, cout, _stream()),
+              "cd360_vae_enc_conv_out_bf16")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- rank-r adapters (add_lora=True)
 LOWRANK_RANKS = (16, 32, 64)
 _DROPOUT_STATE = {}  # device -> int64 [2] (seed, offset) read by the mask of cd360_lowrank_add_bf16 / cd360_dropout_apply_bf16

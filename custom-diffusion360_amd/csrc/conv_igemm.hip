@@ -29,7 +29,8 @@ struct ConvParams {
   uint16_t* out;          // [M, Cout]
   float* stats;           // optional [n_mtiles * slabs_per_tile, Cout, 2]: per-slab channel sums / sums of squares of `out`
   int N, H, W, Cin, Cout, taps;
-  int stride, Ho, Wo;     // output pixel (yo, xo) reads input (stride*yo + ky - 1, stride*xo + kx - 1); Ho = H / stride, Wo = W / stride
+  int stride, Ho, Wo;     // output pixel (yo, xo) reads input (stride*yo + org + ky - 1, stride*xo + org + kx - 1); Ho = H / stride, Wo = W / stride
+  int org;                // tap-centre origin: 0 (pad 1 on every side), 1 (the first stage's Downsample: pad only past the bottom / right edge)
   long M;
   int n_mtiles, n_ntiles, w_major;
   int kgroup;  // K order: 64-channel chunks per group (cd360_conv_k_order): group outer, tap middle, chunk-in-group inner
@@ -99,8 +100,8 @@ __global__ __launch_bounds__(256 * SPLIT) void conv_igemm_kernel(ConvParams p) {
     const long mc = pok[ps] ? m : 0;
     const int img = (int)(mc / HW), rem = (int)(mc - (long)img * HW);
     const int yo = rem / p.Wo, xo = rem - yo * p.Wo;
-    py[ps] = yo * p.stride;  // input coordinates of the tap centre
-    px[ps] = xo * p.stride;
+    py[ps] = yo * p.stride + p.org;  // input coordinates of the tap centre
+    px[ps] = xo * p.stride + p.org;
     xbase[ps] = (uint32_t)(((((long)img * p.H + py[ps]) * p.W + px[ps]) * p.Cin + chunk * 8) * 2);
   }
 
@@ -363,6 +364,11 @@ extern "C" int cd360_conv_stats_rows(int N, int H, int W, int Cin, int Cout, int
   return rows > 0 ? rows : 128 / cd360_conv_stats_slabs(Cout);
 }
 
+namespace {
+int conv_register_staged(const void* x, const void* w_packed, const void* bias, const void* emb, int64_t emb_stride, const void* res,
+                         void* out, int N, int H, int W, int Cin, int Cout, int taps, int stride, int org, void* tile_stats, void* stream);
+}  // namespace
+
 extern "C" int cd360_conv_igemm_bf16(const void* x, const void* w_packed, const void* bias, const void* emb, int64_t emb_stride, const void* res,
                                      void* out, int N, int H, int W, int Cin, int Cout, int taps, int stride, void* tile_stats, void* stream) {
   CD360_TUNE_SCOPE(stream);
@@ -379,8 +385,17 @@ extern "C" int cd360_conv_igemm_bf16(const void* x, const void* w_packed, const 
     const int rc = cd360_gemm_bf16(x, w_packed, out, (int64_t)N * H * W, Cout, Cin, Cin, Cin, Cout, bias, res, Cout, nullptr, 0, 0, 0.f, nullptr, nullptr, 0, stream);
     if (rc != CD360_ERR_SHAPE) return rc;
   }
-  if ((taps != 9 && taps != 1) || Cin % 64 || Cout % 16) return CD360_ERR_SHAPE;
   if ((stride != 1 && stride != 2) || (stride == 2 && (taps != 9 || H % 2 || W % 2))) return CD360_ERR_SHAPE;
+  return conv_register_staged(x, w_packed, bias, emb, emb_stride, res, out, N, H, W, Cin, Cout, taps, stride, 0, tile_stats, stream);
+}
+
+namespace {
+
+// The register-staged kernel for one call (the caller holds the tuning scope and has checked stride / taps against its own envelope):
+// out [N * (H / stride) * (W / stride), Cout], tap centre of output pixel (yo, xo) at input (stride * yo + org, stride * xo + org).
+int conv_register_staged(const void* x, const void* w_packed, const void* bias, const void* emb, int64_t emb_stride, const void* res,
+                         void* out, int N, int H, int W, int Cin, int Cout, int taps, int stride, int org, void* tile_stats, void* stream) {
+  if ((taps != 9 && taps != 1) || Cin % 64 || Cout % 16) return CD360_ERR_SHAPE;
   if (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)out | (uintptr_t)emb | (uintptr_t)res) % 16) return CD360_ERR_ARG;
   if ((long)N * H * W * Cin * 2 >= (1L << 31) || (long)Cout * taps * Cin * 2 >= (1L << 31)) return CD360_ERR_SHAPE;  // 32-bit buffer offsets
   ConvParams p;
@@ -390,7 +405,7 @@ extern "C" int cd360_conv_igemm_bf16(const void* x, const void* w_packed, const 
   if (emb && (emb_stride < Cout || emb_stride % 8)) return CD360_ERR_SHAPE;  // rows of >= Cout elements, 16-byte aligned
   if (tile_stats && ((long)(H / stride) * (W / stride)) % BM) return CD360_ERR_SHAPE;
   p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.taps = taps;
-  p.stride = stride; p.Ho = H / stride; p.Wo = W / stride;
+  p.stride = stride; p.Ho = H / stride; p.Wo = W / stride; p.org = org;
   p.M = (long)N * p.Ho * p.Wo;  // output pixels
   p.n_mtiles = (int)((p.M + BM - 1) / BM);
   // 160-channel tiles (4 waves of 160 x 32) when Cout is a multiple of 160 but not of 128 (Cout = 320): exact tiling
@@ -433,6 +448,26 @@ extern "C" int cd360_conv_igemm_bf16(const void* x, const void* w_packed, const 
   }
   CD360_LAUNCH_CHECK();
   return CD360_OK;
+}
+
+}  // namespace
+
+// The first stage's Downsample (model.py:74-90): F.pad(x, (0, 1, 0, 1)) then a 3 x 3 / stride 2 / pad 0 convolution, Ho = H / 2, Wo = W / 2
+// (floor).  Output pixel (yo, xo) reads input rows 2 yo .. 2 yo + 2 and columns 2 xo .. 2 xo + 2: the register-staged kernel with the tap
+// centre at (2 yo + 1, 2 xo + 1), whose image-border test reads the row / column past the bottom / right edge as zero -- the pad.
+extern "C" int cd360_vae_downsample_stats_rows(int N, int H, int W, int C) {
+  if (N <= 0 || H < 2 || W < 2 || C <= 0 || C % 64) return 0;
+  if (((long)(H / 2) * (W / 2)) % BM) return 0;  // slabs must not straddle images
+  return BM / cd360_conv_stats_slabs(C);
+}
+
+extern "C" int cd360_vae_downsample_bf16(const void* x, const void* w_packed, const void* bias, void* out, void* tile_stats, int N, int H, int W,
+                                         int C, void* stream) {
+  CD360_TUNE_SCOPE(stream);
+  if (!x || !w_packed || !out || N <= 0 || C <= 0) return CD360_ERR_ARG;
+  if (H < 2 || W < 2 || C % 64) return CD360_ERR_SHAPE;
+  if (tile_stats && cd360_vae_downsample_stats_rows(N, H, W, C) <= 0) return CD360_ERR_SHAPE;
+  return conv_register_staged(x, w_packed, bias, nullptr, 0, nullptr, out, N, H, W, C, C, 9, 2, 1, tile_stats, stream);
 }
 
 // A11: pose_emb_layers(cat[x, xref]) = Linear(2C -> C, no bias) (sgm/modules/attention.py:515-516,634) without the concat:

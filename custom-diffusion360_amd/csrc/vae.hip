@@ -10,6 +10,9 @@
 //                            log2-sum-exp, then attn_single_combine_kernel merges them.
 //   cd360_vae_conv_in_f32    Decoder.conv_in (model.py:651-654, :721): fp32 NCHW latent (Cz <= 8) -> bf16 channels-last, + GroupNorm slab sums.
 //   cd360_vae_conv_out_bf16  Decoder.conv_out (model.py:699-701, :733): bf16 channels-last (after norm_out + SiLU) -> fp32 NCHW, Cout <= 4.
+//   cd360_vae_enc_conv_out_bf16  Encoder.conv_out (model.py:568-574, :600): the same at latent resolution, Cout <= 8, the 9 Cin reduction
+//                            split over the threads of a workgroup (16 pixels per workgroup: a 64^2 latent is 256 workgroups).
+// (The Encoder's Downsample is the register-staged convolution kernel with its tap centre moved: conv_igemm.hip.)
 #include "cd360_common.h"
 
 namespace {
@@ -258,6 +261,70 @@ __global__ __launch_bounds__(256) void vae_conv_out_kernel(const uint16_t* __res
     if (co < Cout) out[((long)b * Cout + co) * HW + p] = acc[co] + (bias ? bias[co] : 0.f);
 }
 
+constexpr int EO_PX = 16;      // output pixels per workgroup
+constexpr int EO_SLICES = 16;  // K slices per pixel (256 threads = 16 pixels x 16 slices)
+constexpr int EO_CHUNK = 128;  // input channels whose weights sit in the LDS at a time
+constexpr int EO_GP = 8 * 8 + 4;  // LDS floats per 8-channel group of one tap: 8 channels x 8 outputs + 16 bytes of padding, so that the
+                                  // slices of one ds_read_b128 lane group read different banks
+
+// x [B][H W][Cin] bf16; w [9][Cin][8] fp32 (tap 3 ky + kx, channel, output channel; columns >= Cout zero); out [B][Cout][H][W] fp32.
+// Grid (ceil(H W / 16), B), 256 threads: thread = (slice s = tid / 16, pixel tid % 16).  Per weight chunk, slice s takes the units
+// u = s, s + 16, ... of (tap, 8-channel group) and accumulates all 8 outputs of its pixel in fp32; the 16 slices of a pixel are summed
+// through the LDS in slice order.  Every sum has a fixed order that does not depend on B: deterministic and batch-invariant.
+__global__ __launch_bounds__(256) void vae_enc_conv_out_kernel(const uint16_t* __restrict__ x, const float* __restrict__ w,
+                                                               const float* __restrict__ bias, float* __restrict__ out, int H, int W, int Cin,
+                                                               int Cout) {
+  __shared__ __attribute__((aligned(16))) float wl[9 * (EO_CHUNK / 8) * EO_GP];
+  __shared__ __attribute__((aligned(16))) float red[EO_SLICES * EO_PX * 8];
+  const int b = blockIdx.y, tid = threadIdx.x, s = tid / EO_PX, pp = tid % EO_PX;
+  const long HW = (long)H * W, p = (long)blockIdx.x * EO_PX + pp;
+  const bool live = p < HW;
+  const int y = live ? (int)(p / W) : 0, xq = live ? (int)(p - (long)y * W) : 0;
+  const uint16_t* xb = x + (long)b * HW * Cin;
+  float acc[8];
+#pragma unroll
+  for (int o = 0; o < 8; ++o) acc[o] = 0.f;
+  for (int c0 = 0; c0 < Cin; c0 += EO_CHUNK) {
+    const int cn = min(EO_CHUNK, Cin - c0), groups = cn / 8;  // Cin % 64 == 0: cn is 64 or 128
+    __syncthreads();
+    for (int i = tid; i < 9 * cn * 2; i += 256) {  // f32x4 units: tap, channel, half of the 8 outputs
+      const int tap = i / (cn * 2), r = i - tap * cn * 2, ci = r >> 1;
+      *reinterpret_cast<f32x4*>(wl + (tap * (EO_CHUNK / 8) + (ci >> 3)) * EO_GP + (ci & 7) * 8 + (r & 1) * 4) =
+          *reinterpret_cast<const f32x4*>(w + ((long)tap * Cin + c0) * 8 + r * 4);
+    }
+    __syncthreads();
+    if (!live) continue;
+    for (int u = s; u < 9 * groups; u += EO_SLICES) {
+      const int tap = u / groups, g = u - tap * groups;
+      const int yy = y + tap / 3 - 1, xx = xq + tap % 3 - 1;
+      if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+      const u32x4 v = *reinterpret_cast<const u32x4*>(xb + ((long)yy * W + xx) * Cin + c0 + g * 8);
+      const float* wg = wl + (tap * (EO_CHUNK / 8) + g) * EO_GP;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float xv = (e & 1) ? bf16hi_to_f32(v[e >> 1]) : bf16lo_to_f32(v[e >> 1]);
+        const f32x4 w0 = *reinterpret_cast<const f32x4*>(wg + e * 8), w1 = *reinterpret_cast<const f32x4*>(wg + e * 8 + 4);
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+          acc[o] = fmaf(xv, w0[o], acc[o]);
+          acc[4 + o] = fmaf(xv, w1[o], acc[4 + o]);
+        }
+      }
+    }
+  }
+  *reinterpret_cast<f32x4*>(red + (s * EO_PX + pp) * 8) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+  *reinterpret_cast<f32x4*>(red + (s * EO_PX + pp) * 8 + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+  __syncthreads();
+  if (tid >= EO_PX * 8) return;
+  const int op = tid % EO_PX, co = tid / EO_PX;  // consecutive threads: consecutive pixels of one output channel (coalesced stores)
+  const long po = (long)blockIdx.x * EO_PX + op;
+  if (co >= Cout || po >= HW) return;
+  float sum = 0.f;
+#pragma unroll
+  for (int k = 0; k < EO_SLICES; ++k) sum += red[(k * EO_PX + op) * 8 + co];
+  out[((long)b * Cout + co) * HW + po] = sum + (bias ? bias[co] : 0.f);
+}
+
 }  // namespace
 
 extern "C" int cd360_attn_single_splits(int B, int N) {
@@ -335,6 +402,19 @@ extern "C" int cd360_vae_conv_out_bf16(const void* x, const void* w, const void*
   if (((uintptr_t)x | (uintptr_t)w) % 16) return CD360_ERR_ARG;
   const dim3 grid((unsigned)(((long)H * W + 255) / 256), B);
   vae_conv_out_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const uint16_t*)x, (const float*)w, (const float*)bias, (float*)out, H, W, Cin, Cout);
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+extern "C" int cd360_vae_enc_conv_out_bf16(const void* x, const void* w, const void* bias, void* out, int B, int H, int W, int Cin, int Cout,
+                                           void* stream) {
+  if (!x || !w || !out || B <= 0 || H <= 0 || W <= 0) return CD360_ERR_ARG;
+  if (Cin % 64 || Cin <= 0 || Cout < 1 || Cout > 8 || B > 65535) return CD360_ERR_SHAPE;
+  if (((uintptr_t)x | (uintptr_t)w) % 16) return CD360_ERR_ARG;
+  const long blocks = ((long)H * W + EO_PX - 1) / EO_PX;
+  if (blocks > 0x7fffffffL) return CD360_ERR_SHAPE;
+  vae_enc_conv_out_kernel<<<dim3((unsigned)blocks, B), 256, 0, (hipStream_t)stream>>>((const uint16_t*)x, (const float*)w, (const float*)bias,
+                                                                                     (float*)out, H, W, Cin, Cout);
   CD360_LAUNCH_CHECK();
   return CD360_OK;
 }

@@ -1,5 +1,6 @@
 """The first stage's autoencoder network (reference sgm/modules/diffusionmodules/model.py) on the HIP kernels: `Decoder` serves
-`AutoencoderKL.decode` (sgm/models/autoencoder.py:295-296, diffusion.py:208-212), so `decode_first_stage` runs without xformers.
+`AutoencoderKL.decode` (sgm/models/autoencoder.py:295-296, diffusion.py:208-212) and `Encoder` serves `AutoencoderKL.encode`
+(encode_first_stage, diffusion.py:238-248), so neither needs xformers.
 
 Constructors, attribute names and state_dict keys are the reference's, so checkpoints load unchanged.  Activations travel between the
 submodules as NCHW-shaped bf16 tensors in torch.channels_last memory format -- physically the channels-last rows [N, H W, C] the kernels
@@ -10,12 +11,13 @@ A submodule called on its own with another dtype or layout converts its input on
                     (x, or the nin_shortcut 1x1 / conv_shortcut 3x3 output when in != out)
   Attn blocks       GroupNorm -> ONE q|k|v 1x1 GEMM (q rows prescaled) -> cd360_attn_single_bf16 -> proj_out 1x1 + residual x
   Upsample          cd360_conv_up2x_bf16 (nearest 2x folded into four 2x2-tap phases)
+  Downsample        cd360_vae_downsample_bf16 (pad (0, 1, 0, 1) + 3x3 / stride 2; emits the next norm1's GroupNorm slab sums)
   Decoder ends      cd360_vae_conv_in_f32 (fp32 NCHW latent in) and norm_out + SiLU -> cd360_vae_conv_out_bf16 (fp32 NCHW out)
+  Encoder ends      cd360_vae_conv_in_f32 (fp32 NCHW image in) and norm_out + SiLU -> cd360_vae_enc_conv_out_bf16 (fp32 NCHW moments)
 
 Packed weights are cached per module, keyed on the parameters' (data_ptr, _version): load_state_dict or an in-place copy_ repacks.
 An edit through `p.data` is NOT seen: `.data` is a tensor with a version counter of its own (as for UNetModel._emb_cat).
-Forward only: a call autograd would have to record raises (decode_first_stage runs under no_grad).  Encoder is constructible (so that
-AutoencoderKL.__init__ works and checkpoints load); its forward is not implemented."""
+Forward only: a call autograd would have to record raises (decode_first_stage and encode_first_stage run under no_grad)."""
 from __future__ import annotations
 
 import torch
@@ -113,7 +115,13 @@ class Downsample(nn.Module):
             self.conv = torch.nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=2, padding=0)
 
     def forward(self, x):
-        raise NotImplementedError("Downsample belongs to Encoder.forward (encode_first_stage), which this package does not serve")
+        if not self.with_conv:
+            raise NotImplementedError("Downsample(with_conv=False) is not used by the first stage (resamp_with_conv=True)")
+        _check_no_grad(self)
+        rows, n, c, h, w = _rows(x)
+        wp, b = _packed(self, (self.conv.weight, self.conv.bias), lambda: _conv_pack(self.conv))
+        out, st = ops.vae_downsample(rows, wp, b, n, h, w)
+        return _with_stats(_nchw(out, n, h // 2, w // 2), st)
 
 
 class ResnetBlock(nn.Module):
@@ -264,8 +272,65 @@ class Encoder(nn.Module):
         self.norm_out = Normalize(block_in)
         self.conv_out = torch.nn.Conv2d(block_in, 2 * z_channels if double_z else z_channels, kernel_size=3, stride=1, padding=1)
 
+    def pass_bytes(self, h: int, w: int) -> int:
+        """Largest tensor the convolution cores address for one h x w image (every block input / output, each q|k|v projection); it must
+        stay below 2^31 bytes.  At the SDXL ddconfig that is the level-0 activation, h w 128 channels of bf16."""
+        hw = h * w
+        biggest = hw * self.conv_in.out_channels * 2
+        for i_level in range(self.num_resolutions):
+            down = self.down[i_level]
+            for blk in down.block:
+                biggest = max(biggest, hw * max(blk.in_channels, blk.out_channels) * 2)
+                if len(down.attn) > 0:
+                    biggest = max(biggest, hw * 3 * blk.out_channels * 2)
+            if i_level != self.num_resolutions - 1:
+                h, w = h // 2, w // 2
+                hw = h * w
+        return max(biggest, hw * 3 * self.mid.block_1.out_channels * 2)
+
     def forward(self, x):
-        raise NotImplementedError("Encoder.forward (encode_first_stage, training only) is not implemented on HIP")
+        if not x.is_cuda:
+            raise NotImplementedError("Encoder.forward runs on the HIP kernels only; got a host tensor")
+        _check_no_grad(self)
+        # one image per pass, as in Decoder.forward: an image encodes to the same bits in a batch of any size (the target x and the
+        # references xr of shared_step call this with different batch sizes)
+        if x.shape[0] == 1:
+            return self._encode_pass(x)
+        return torch.cat([self._encode_pass(x[i:i + 1]) for i in range(x.shape[0])], 0)
+
+    def _encode_pass(self, x):
+        n, cin, h, w = x.shape
+        if self.pass_bytes(h, w) >= _INT32_BYTES:
+            raise ops.Cd360Error(f"an image of {h} x {w} exceeds the 32-bit offsets of the convolution cores")
+        temb = None
+
+        win, bin_, wout, bout = _packed(self, (self.conv_in.weight, self.conv_in.bias, self.conv_out.weight, self.conv_out.bias), lambda: (
+            ops.pack_vae_conv_in_weight(self.conv_in.weight), ops.bias_f32(self.conv_in.bias).clone(),
+            ops.pack_vae_enc_conv_out_weight(self.conv_out.weight), ops.bias_f32(self.conv_out.bias).clone()))
+        x32 = x.float().contiguous()
+        if (h * w) % 64 == 0:
+            rows, st = ops.vae_conv_in(x32, win, bin_, want_stats=True)
+        else:
+            rows, st = ops.vae_conv_in(x32, win, bin_), None
+        hid = _with_stats(_nchw(rows, n, h, w), st)
+
+        # the reference keeps every level's output in a list `hs`; only its last entry is ever read
+        for i_level in range(self.num_resolutions):
+            for i_block in range(self.num_res_blocks):
+                hid = self.down[i_level].block[i_block](hid, temb)
+                if len(self.down[i_level].attn) > 0:
+                    hid = self.down[i_level].attn[i_block](hid)
+            if i_level != self.num_resolutions - 1:
+                hid = self.down[i_level].downsample(hid)
+
+        hid = self.mid.block_1(hid, temb)
+        hid = self.mid.attn_1(hid)
+        hid = self.mid.block_2(hid, temb)
+
+        rows, n, c, hh, ww = _rows(hid)
+        act = _gn(self.norm_out, rows, True)
+        out = ops.vae_enc_conv_out(act, wout, bout, n, hh, ww, self.conv_out.out_channels)
+        return out.to(self.conv_out.weight.dtype)
 
 
 class Decoder(nn.Module):

@@ -70,7 +70,7 @@ int cd360_get_tuning(cd360_tuning* t);
  * removes the override; at most 16 streams; thread-safe.  cd360_get_stream_tuning returns what launches on `stream` read (override or
  * default).  The shape queries below that size a buffer for a following launch (cd360_gemm_tile_n, cd360_gemm_cstats_rows,
  * cd360_conv_stats_slabs, cd360_conv_stats_rows, cd360_conv_dma_slab_rows, cd360_conv_route, cd360_conv3x3_dma_route, cd360_conv_up2x_route,
- * cd360_conv_k_order) take no stream: on the CALLING THREAD they answer for the stream named by the last cd360_query_stream (NULL or a
+ * cd360_conv_k_order, cd360_vae_downsample_stats_rows) take no stream: on the CALLING THREAD they answer for the stream named by the last cd360_query_stream (NULL or a
  * stream without override: the default) -- thread-local state only. */
 int cd360_set_stream_tuning(void* stream, const cd360_tuning* t);
 int cd360_get_stream_tuning(void* stream, cd360_tuning* t);
@@ -164,6 +164,24 @@ int cd360_vae_conv_in_f32(const void* z, const void* w, const void* bias, void* 
  * [9, Cin, 4] (tap 3 ky + kx, channel, output channel; columns >= Cout zero); bias fp32 [Cout] | NULL -> out fp32 NCHW [B, Cout, H, W].
  * Cout <= 4, any H and W. */
 int cd360_vae_conv_out_bf16(const void* x, const void* w, const void* bias, void* out, int B, int H, int W, int Cin, int Cout, void* stream);
+
+/* ---- the first-stage encoder (AutoencoderKL.encode -> Encoder.forward, model.py:487-601) ------------------------------------------
+ * Encoder.conv_in runs on cd360_vae_conv_in_f32 (3 image channels), its blocks on the decoder's kernels.
+ * replaces Downsample.forward with_conv=True (model.py:74-90): F.pad(x, (0, 1, 0, 1)) then Conv2d(C -> C, 3 x 3, stride 2, padding 0).
+ * x bf16 channels-last [N, H W, C]; w_packed bf16 [C, 9 C] in the K order of cd360_conv_igemm_bf16 (cd360.ops.pack_conv_weight);
+ * bias fp32 [C] | NULL -> out bf16 [N, (H / 2) (W / 2), C] (floor: odd sizes drop their last row / column like the reference).
+ * C % 64 == 0, H, W >= 2.  tile_stats (optional, NULL to skip): fp32 [N (H/2) (W/2) / rows, C, 2] per-slab channel sums / sums of
+ * squares of the bf16 outputs with rows = cd360_vae_downsample_stats_rows(N, H, W, C) (0: this shape has no slabs, pass NULL), for the
+ * cd360_gn_silu_bf16 of the next ResnetBlock's norm1.  The query follows the cd360_query_stream rule above. */
+int cd360_vae_downsample_stats_rows(int N, int H, int W, int C);
+int cd360_vae_downsample_bf16(const void* x, const void* w_packed, const void* bias, void* out, void* tile_stats, int N, int H, int W, int C,
+                              void* stream);
+/* replaces Encoder.conv_out (model.py:568-574, applied at :598-600 behind norm_out + nonlinearity): Conv2d(Cin -> Cout, 3 x 3, padding 1)
+ * writing the tensor Encoder.forward returns (the moments of the posterior before quant_conv).  x bf16 channels-last [B, H W, Cin]
+ * (after GroupNorm + SiLU), Cin % 64 == 0; w fp32 [9, Cin, 8] (tap 3 ky + kx, channel, output channel; columns >= Cout zero); bias fp32
+ * [Cout] | NULL -> out fp32 NCHW [B, Cout, H, W].  Cout <= 8, any H and W.  fp32 accumulation in a fixed order: deterministic, and an
+ * image's output does not depend on B. */
+int cd360_vae_enc_conv_out_bf16(const void* x, const void* w, const void* bias, void* out, int B, int H, int W, int Cin, int Cout, void* stream);
 
 /* ---- rays, projection, integer bilinear indices ----------------------------------------------------------------
  * replaces get_patch_rays / get_patch_raybundle / get_directional_raybundle  (sgm/modules/utils_cameraray.py:61-196)

@@ -8,7 +8,12 @@ decodes, warm-up first, at least --min-seconds of timed work per column) and the
 (FLOP = 4 N^2 C B) from the HIP path's per-launch events (cd360.ops.profile_start: attention kernel + combine kernel).  For batch 2
 also the max relative error of the per-image decode and of the batch-folded pass against the fp32 restatement.  Kernel times proper come
 from a separate `rocprofv3 --kernel-trace --stats --output-format csv -- python tools/bench_vae.py --profile-only` (one decode per case):
-the new kernels are attn_single_kernel<512>, attn_single_combine_kernel, vae_conv_in_kernel and vae_conv_out_kernel."""
+the new kernels are attn_single_kernel<512>, attn_single_combine_kernel, vae_conv_in_kernel and vae_conv_out_kernel.
+
+Encoder section (Encoder.forward, model.py:487-601, against tests/vae_enc_fp32.py): image 512^2 / 1024^2, batch 1 / 5 (the target x and the
+b*n reference images of shared_step): ms per image of both encoders and the max relative error of the HIP encoder against fp32.  Its
+kernels in the rocprofv3 run: conv_igemm_kernel (the Downsamples among the other convolutions), vae_enc_conv_out_kernel and
+vae_conv_in_kernel (here reading the 3-channel image).  --section decoder | encoder | all (default)."""
 import argparse
 import json
 import os
@@ -22,14 +27,16 @@ for p in (ROOT, os.path.join(ROOT, "custom-diffusion360_amd"), os.path.join(ROOT
 
 import torch  # noqa: E402
 
+import vae_enc_fp32  # noqa: E402
 import vae_fp32  # noqa: E402
 import weights as W  # noqa: E402
 from cd360 import ops  # noqa: E402
-from sgm.modules.diffusionmodules.model import Decoder  # noqa: E402
+from sgm.modules.diffusionmodules.model import Decoder, Encoder  # noqa: E402
 
 DDCONFIG = dict(attn_type="vanilla-xformers", double_z=True, z_channels=4, resolution=256, in_channels=3, out_ch=3, ch=128,
                 ch_mult=[1, 2, 4, 4], num_res_blocks=2, attn_resolutions=[], dropout=0.0)
 CASES = [(64, 1), (64, 2), (128, 1), (128, 2)]
+ENC_CASES = [(512, 1), (512, 5), (1024, 1), (1024, 5)]
 
 
 def timed(fn, min_seconds):
@@ -54,8 +61,51 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--profile-only", action="store_true", help="one decode per case, HIP path only (for rocprofv3)")
     ap.add_argument("--no-baseline", action="store_true")
+    ap.add_argument("--section", choices=("decoder", "encoder", "all"), default="all")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    rows = []
+    if a.section in ("decoder", "all"):
+        rows += bench_decoder(a, dev)
+    if a.section in ("encoder", "all"):
+        rows += bench_encoder(a, dev)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+def bench_encoder(a, dev):
+    enc = Encoder(**DDCONFIG).eval()
+    sd = W.load_into(enc, 3)
+    enc = enc.to(dev)
+    sd = {k: v.to(dev) for k, v in sd.items()}
+    rows = []
+    with torch.no_grad():
+        for hw, b in ENC_CASES:
+            x = W.tensor(f"x{hw}", (b, 3, hw, hw), seed=1).to(dev)
+            if a.profile_only:
+                enc(x)
+                torch.cuda.synchronize()
+                continue
+            ms = timed(lambda: enc(x), a.min_seconds)
+            ops.profile_start()
+            enc(x)
+            prof = ops.profile_stop()
+            r = {"section": "encoder", "image": hw, "batch": b, "hip_ms_per_image": ms / b,
+                 "hip_event_ms_per_image": {k: v["ms"] / b for k, v in sorted(prof.items())}}
+            if not a.no_baseline:
+                torch.backends.cuda.matmul.allow_tf32 = torch.backends.cudnn.allow_tf32 = False
+                base = timed(lambda: vae_enc_fp32.encode(sd, x, DDCONFIG["ch_mult"], 2), a.min_seconds)
+                want = vae_enc_fp32.encode(sd, x, DDCONFIG["ch_mult"], 2)
+                got = enc(x)
+                r["fp32_framework_ms_per_image"] = base / b
+                r["max_rel_err_vs_fp32"] = ((got - want).abs().max() / want.abs().max()).item()
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+    return rows
+
+
+def bench_decoder(a, dev):
     dec = Decoder(**DDCONFIG).eval()
     sd = W.load_into(dec, 3)
     dec = dec.to(dev)
@@ -82,14 +132,12 @@ def main():
                 per, folded = dec(z), dec._decode_pass(z)
                 rel = lambda x, y: ((x - y).abs().max() / y.abs().max()).item()
                 acc = {"per_image_err_vs_fp32": rel(per, want), "folded_err_vs_fp32": rel(folded, want), "folded_vs_per_image": rel(folded, per)}
-            r = {"image": 8 * hw, "batch": b, "hip_ms_per_image": ms / b, "fp32_framework_ms_per_image": None if base is None else base / b,
+            r = {"section": "decoder", "image": 8 * hw, "batch": b, "hip_ms_per_image": ms / b, "fp32_framework_ms_per_image": None if base is None else base / b,
                  "attn_ms": att["ms"], "attn_tflops": att["flops"] / att["ms"] / 1e9 if att["ms"] > 0 else None,
                  "attn_splits": ops.attention_single_splits(b, hw * hw), "max_batch_per_pass_computed": dec.max_batch(hw, hw), **acc}
             rows.append(r)
             print(json.dumps(r), flush=True)
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(rows, f, indent=1)
+    return rows
 
 
 if __name__ == "__main__":
