@@ -18,7 +18,10 @@ from . import shard
 
 
 class Sampler:
-    """Minimal Euler (DDIM-equivalent, EpsScaling) step with the 3-way image/text CFG of guiders.py:102-133.
+    """Minimal Euler (DDIM-equivalent, EpsScaling) step with the 3-way image/text CFG of guiders.py:102-133 (uncond | image | image+text)
+    or, for `scale_im is None or scale_im <= 0`, the 2-way VanillaCFGImgRef of guiders.py:136-166 (uncond | image+text) -- the switch of
+    sample.py:231-240.  B = guider.branches: `ctx` / `y` hold B bs rows ([uc x bs | . | c x bs] resp. [uc x bs | c x bs]), `pose` B bs camera
+    batches, and the UNet runs on B bs images (two branches: a third less work per step, not a duplicated branch).
     With `use_graph` the steady-state step (cached render) and the render step are each captured once into a hipGraph and
     replayed: ~3000 launches per step are then issued by the GPU front end instead of the Python interpreter."""
 
@@ -32,11 +35,18 @@ class Sampler:
         dev = ctx.device
         # the reference's own stack (cd360/sampler.py mirrors sampling.py / guiders.py / denoiser.py; parity: tests/test_sampler_cpu.py)
         self.denoiser = S.DiscreteDenoiser().to(dev)
-        self.guider = S.ScheduledCFGImgTextRef(scale, scale_im)
+        two = scale_im is None or scale_im <= 0  # sample.py:231-240
+        self.guider = S.VanillaCFGImgRef(scale) if two else S.ScheduledCFGImgTextRef(scale, scale_im)
+        self.branches = nb = self.guider.branches
+        if two:
+            self.scale_im = None  # (the tail kernels' two-branch request)
+        if ctx.shape[0] % nb or y.shape[0] != ctx.shape[0] or (isinstance(pose, (list, tuple)) and len(pose) != ctx.shape[0]):
+            raise ValueError(f"the {nb}-branch guider takes ctx / y / pose of {nb} x bs rows, got {ctx.shape[0]} / {y.shape[0]} / "
+                             f"{len(pose) if isinstance(pose, (list, tuple)) else '?'}")
         self.sigmas = S.LegacyDDPMDiscretization()(n_steps, device=dev)  # n_steps + 1 values, last = 0
-        # conditioning is constant over a trajectory: the guider's (uc, uc, c) batch is assembled once per image, not per step
-        self.bs = bs = ctx.shape[0] // 3  # diffusion samples (target poses) per replay: ctx / y hold [uc x bs | . | c x bs]
-        c = {"crossattn": ctx[2 * bs:], "vector": y[2 * bs:]}
+        # conditioning is constant over a trajectory: the guider's (uc, uc, c) / (uc, c) batch is assembled once per image, not per step
+        self.bs = bs = ctx.shape[0] // nb  # diffusion samples (target poses) per replay: ctx / y hold [uc x bs | . | c x bs] / [uc x bs | c x bs]
+        c = {"crossattn": ctx[(nb - 1) * bs:], "vector": y[(nb - 1) * bs:]}
         uc = {"crossattn": ctx[:bs], "vector": y[:bs]}
         _, _, cond3 = self.guider.prepare_inputs(ctx.new_zeros(bs, 1), ctx.new_zeros(bs), c, uc)
         self.ctx, self.y = cond3["crossattn"].contiguous(), cond3["vector"].contiguous()
@@ -48,13 +58,21 @@ class Sampler:
         # eager launches (use_graph=False) run the same staged step
         from cd360 import routes
         self.staged = bool(not routes.no_stage and self._stageable())
+        self._state_layout()
+
+    def _state_layout(self):
+        """Tell the pose blocks how this sampler's CFG batch is laid out (B bs rows, the first bs unconditional) instead of leaving them to
+        infer it from `batch % 3`: six rows are two branches of three poses as well as three branches of two.  Restated before every
+        render, so samplers of both guiders can share one UNet."""
+        from cd360 import sampling
+        sampling.set_cfg_branches(self.net, self.branches)
 
     def retarget(self, pose, ctx, y):
         """Point the sampler at another target pose / conditioning (the next pose of this rank's share).  The captured graphs read both
         through fixed device buffers, so the new values are copied INTO them: the CFG conditioning batch, and the packed
-        [3, n+1, 16] camera tensor this sampler owns (sgm/modules/utils_cameraray.py::PoseBuffer)."""
-        bs = self.bs
-        c = {"crossattn": ctx[2 * bs:], "vector": y[2 * bs:]}
+        [B bs, n+1, 16] camera tensor this sampler owns (sgm/modules/utils_cameraray.py::PoseBuffer)."""
+        bs, nb = self.bs, self.branches
+        c = {"crossattn": ctx[(nb - 1) * bs:], "vector": y[(nb - 1) * bs:]}
         uc = {"crossattn": ctx[:bs], "vector": y[:bs]}
         _, _, cond3 = self.guider.prepare_inputs(ctx.new_zeros(bs, 1), ctx.new_zeros(bs), c, uc)
         self.ctx.copy_(cond3["crossattn"])
@@ -91,7 +109,7 @@ class Sampler:
             _, _, c_in, c_noise = self.denoiser.scaling(sq)
             c_noise = self.denoiser.possibly_quantize_c_noise(c_noise)
             rows.append(torch.stack([self.sigmas[i], self.sigmas[i + 1], c_in[0], torch.zeros_like(c_in[0])]))
-            tembs.append(net.time_embed(timestep_embedding(c_noise.expand(3), net.model_channels).to(dt))[0])
+            tembs.append(net.time_embed(timestep_embedding(c_noise.expand(self.branches), net.model_channels).to(dt))[0])
         self.step_tab = torch.stack(rows).float().contiguous()
         self.temb_tab = torch.stack(tembs).to(dt).contiguous()
         self._iota = torch.arange(self.n_steps, dtype=torch.int32, device=dev)
@@ -100,12 +118,12 @@ class Sampler:
         self.w36 = conv.weight.detach().float().permute(2, 3, 1, 0).reshape(36, conv.out_channels).contiguous()
         self.b_in = (conv.bias.detach().float() if conv.bias is not None else torch.zeros(conv.out_channels, device=dev)).contiguous()
         self.lab = net.label_emb(self.y.to(dt)).contiguous()
-        bs3, (H, W) = self.y.shape[0], x.shape[2:]
-        self.h0 = torch.empty(bs3, H * W, conv.out_channels, dtype=dt, device=dev)
+        nbs, (H, W) = self.y.shape[0], x.shape[2:]  # B bs images
+        self.h0 = torch.empty(nbs, H * W, conv.out_channels, dtype=dt, device=dev)
         self.emb_act = torch.empty_like(self.lab)
 
     def _math_staged(self):
-        """One sampler step on the static buffers, in place on self.gx: stage-in kernel -> UNet trunk -> fused [c_out, 3-way CFG, to_d,
+        """One sampler step on the static buffers, in place on self.gx: stage-in kernel (rep = B) -> UNet trunk -> fused [c_out, CFG, to_d,
         Euler] kernel reading the output convolution's rows as they lie."""
         from cd360 import ops
         H, W = self.gx.shape[2:]
@@ -115,15 +133,17 @@ class Sampler:
 
     def _math(self, x, s, s_next, t_unused=None):
         """One sampler step = guider.prepare_inputs -> DiscreteDenoiser (sigma -> table index, c_in) -> UNet -> fused
-        [c_out, 3-way CFG, to_d, Euler] kernel."""
-        from cd360.sampler import fused_cfg3_euler_step
+        [c_out, CFG, to_d, Euler] kernel."""
+        from cd360.sampler import fused_cfg_euler_step
         unet = lambda x_in, c_noise: self.net(x_in, timesteps=c_noise, context=self.ctx, y=self.y, pose=self.pose)[0]  # noqa: E731
-        return fused_cfg3_euler_step(self.denoiser, unet, x, s, s_next, self.scale, self.scale_im)
+        return fused_cfg_euler_step(self.denoiser, unet, x, s, s_next, self.guider)
 
     @torch.no_grad()
     def eps(self, x, i):
-        """The UNet's output for step i of the schedule (the three CFG branches), launched eagerly: what --fp8-attn's tolerance report compares."""
-        x3 = x.expand(3, -1, -1, -1) if x.shape[0] == 1 else torch.cat([x] * 3)
+        """The UNet's output for step i of the schedule (the guider's CFG branches), launched eagerly: what --fp8-attn's tolerance report compares."""
+        nb = self.branches
+        self._state_layout()
+        x3 = x.expand(nb, -1, -1, -1) if x.shape[0] == 1 else torch.cat([x] * nb)
         x_in, c_noise, _, _, _ = self.denoiser.network_inputs(x3, self.sigmas[i].expand(x3.shape[0]), {})
         return self.net(x_in, timesteps=c_noise, context=self.ctx, y=self.y, pose=self.pose)[0].float()
 
@@ -179,6 +199,7 @@ class Sampler:
         """Step 0 of an image: clear the cached render, run the full step (all 12 FeatureNeRF renders), re-pin the caches."""
         from cd360 import sampling
         sampling.clear_rendered_feat(self.net)
+        self._state_layout()
         out = self._math_staged() if self.staged else self._math(self.gx, self.gs[0], self.gs[1], self.gt)
         self._pin_rendered()
         return out
@@ -239,6 +260,7 @@ class Sampler:
                 if i == 0:
                     from cd360 import sampling
                     sampling.clear_rendered_feat(self.net)
+                    self._state_layout()
                 self._math_staged()
             elif i == 0:
                 if self.rgraph is not None:
@@ -253,6 +275,7 @@ class Sampler:
             if i == 0:
                 from cd360 import sampling
                 sampling.clear_rendered_feat(self.net)  # new image: the render runs again
+                self._state_layout()
             return self._math(x, s, s_next, t)
         self.prepare(x)
         self.gx.copy_(x)

@@ -4,6 +4,7 @@ No operator here has a PyTorch/CPU implementation: a CPU tensor (or a missing li
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import NamedTuple, Optional
 
 import torch
@@ -1208,14 +1209,29 @@ def add_layernorm_bwd(x: torch.Tensor, gamma: torch.Tensor, d_ln: torch.Tensor, 
     return dx
 
 
-def cfg_euler_step(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, scale: float, scale_im: float):
-    """x [n,...] fp32, eps [3n,...] fp32 (u | ic | c), sigma / sigma_next 0-d fp32 device tensors -> Euler-updated x (one kernel)."""
+def _cfg_branches(scale_im: Optional[float]) -> int:
+    """3 (ScheduledCFGImgTextRef: u | ic | c) or, for scale_im=None, 2 (VanillaCFGImgRef: u | c).  The C entry points take the two-branch
+    request as a NaN scale_im (include/cd360_hip.h), so a NaN handed in as a NUMBER is refused here rather than read as that request."""
+    if scale_im is None:
+        return 2
+    if math.isnan(float(scale_im)):
+        raise ValueError("scale_im is NaN; pass scale_im=None for the two-branch (VanillaCFGImgRef) step")
+    return 3
+
+
+def cfg_euler_step(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, scale: float, scale_im: Optional[float]):
+    """x [n,...] fp32, eps [3n,...] fp32 (u | ic | c) or, with scale_im=None, [2n,...] (u | c), sigma / sigma_next 0-d fp32 device tensors
+    -> Euler-updated x (one kernel)."""
     _need_gpu(x, eps, sigma, sigma_next)
-    assert x.dtype == torch.float32 and eps.dtype == torch.float32 and eps.numel() == 3 * x.numel() and x.is_contiguous() and eps.is_contiguous()
+    nb = _cfg_branches(scale_im)
+    if eps.shape[0] != nb * x.shape[0] or eps.numel() != nb * x.numel():
+        raise ValueError(f"eps holds {eps.shape[0]} rows of {tuple(eps.shape[1:])}; the {nb}-branch step on x {tuple(x.shape)} needs {nb * x.shape[0]}")
+    assert x.dtype == torch.float32 and eps.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
     assert sigma.dtype == torch.float32 and sigma_next.dtype == torch.float32 and sigma.numel() == 1 and sigma_next.numel() == 1
     out = torch.empty_like(x)
-    check(_lib.load().cd360_cfg_euler_step_f32(_ptr(x), _ptr(eps), _ptr(sigma), _ptr(sigma_next), float(scale), float(scale_im), _ptr(out),
-                                              x.numel(), _stream()), "cd360_cfg_euler_step_f32")
+    check(_lib.load().cd360_cfg_euler_step_f32(_ptr(x), _ptr(eps), _ptr(sigma), _ptr(sigma_next), float(scale),
+                                              float("nan") if nb == 2 else float(scale_im), _ptr(out), x.numel(), _stream()),
+          "cd360_cfg_euler_step_f32")
     return out
 
 
@@ -1236,18 +1252,22 @@ def unet_stage_in(x: torch.Tensor, step_tab: torch.Tensor, step: torch.Tensor, w
     return h, emb_act
 
 
-def cfg_euler_step_cl(x: torch.Tensor, eps_cl: torch.Tensor, step_tab: torch.Tensor, step: torch.Tensor, scale: float, scale_im: float):
+def cfg_euler_step_cl(x: torch.Tensor, eps_cl: torch.Tensor, step_tab: torch.Tensor, step: torch.Tensor, scale: float, scale_im: Optional[float]):
     """Tail of a captured sampling step, IN PLACE on x [bs, 4, H, W] fp32: eps_cl [3 bs, H W, >= 4] bf16 channels-last rows (a channel slice
-    of wider rows is fine: the row stride is passed), sigma / sigma_next = step_tab[step][0 / 1]  (cd360_cfg_euler_step_cl)."""
+    of wider rows is fine: the row stride is passed) or, with scale_im=None, [2 bs, H W, >= 4] (u | c), sigma / sigma_next =
+    step_tab[step][0 / 1]  (cd360_cfg_euler_step_cl)."""
     _need_gpu(x, eps_cl, step_tab, step)
+    nb = _cfg_branches(scale_im)
     bs = x.shape[0]
     hw = x.shape[2] * x.shape[3]
+    if eps_cl.shape[0] != nb * bs:
+        raise ValueError(f"eps_cl holds {eps_cl.shape[0]} images; the {nb}-branch step on {bs} latents needs {nb * bs}")
     assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == 4 and eps_cl.dtype == torch.bfloat16
-    assert eps_cl.shape[0] == 3 * bs and eps_cl.shape[1] == hw and eps_cl.shape[2] >= 4 and eps_cl.stride(2) == 1
+    assert eps_cl.shape[1] == hw and eps_cl.shape[2] >= 4 and eps_cl.stride(2) == 1
     ld = eps_cl.stride(1)
     assert eps_cl.stride(0) == hw * ld
-    check(_lib.load().cd360_cfg_euler_step_cl(_ptr(x), _ptr(eps_cl), _ptr(step_tab), _ptr(step), float(scale), float(scale_im), bs, hw, ld,
-                                             _stream()), "cd360_cfg_euler_step_cl")
+    check(_lib.load().cd360_cfg_euler_step_cl(_ptr(x), _ptr(eps_cl), _ptr(step_tab), _ptr(step), float(scale),
+                                             float("nan") if nb == 2 else float(scale_im), bs, hw, ld, _stream()), "cd360_cfg_euler_step_cl")
     return x
 
 

@@ -6,7 +6,7 @@ Reference: EulerEDMSampler (sgm/modules/diffusionmodules/sampling.py:23-136,314-
 custom-diffusion360_amd/sgm/modules/diffusionmodules/), so the YAML sampler/denoiser/guider configs resolve unchanged.
 
 Everything stays on the device and nothing synchronises: the sigma -> index quantisation is an argmin + gather on the GPU, and
-with `fused=True` the per-step tail (c_out scaling, 3-way CFG combine, to_d, Euler update) is one HIP kernel
+with `fused=True` the per-step tail (c_out scaling, 3-way or 2-way CFG combine, to_d, Euler update) is one HIP kernel
 (cd360_cfg_euler_step_f32) instead of ~10 tiny elementwise launches.
 """
 from __future__ import annotations
@@ -221,33 +221,60 @@ class EulerEDMSampler:
     forward = __call__
 
 
-def cfg_euler_update(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, scale: float, scale_im: float,
-                     fused: bool = True) -> torch.Tensor:
-    """One fused tail of a 3-way-CFG Euler step with EpsScaling: x [n,...] fp32, eps [3n,...] (u | ic | c) network output,
-    sigma / sigma_next 0-d device tensors.  den_b = x - sigma eps_b; d0 = den_u + scale (den_c - den_ic) + scale_im (den_ic - den_u);
-    x' = x + (x - d0) / sigma * (sigma_next - sigma)."""
+def cfg_euler_update(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, scale: float,
+                     scale_im: Optional[float] = None, fused: bool = True) -> torch.Tensor:
+    """One fused tail of a CFG Euler step with EpsScaling: x [n,...] fp32, sigma / sigma_next 0-d device tensors, den_b = x - sigma eps_b,
+    x' = x + (x - d0) / sigma * (sigma_next - sigma) with
+      scale_im a number (ScheduledCFGImgTextRef):  eps [3n,...] (u | ic | c),  d0 = den_u + scale (den_c - den_ic) + scale_im (den_ic - den_u)
+      scale_im=None     (VanillaCFGImgRef):        eps [2n,...] (u | c),       d0 = den_u + scale (den_c - den_u)."""
+    nb = 2 if scale_im is None else 3
+    if eps.shape[0] != nb * x.shape[0]:
+        raise ValueError(f"eps holds {eps.shape[0]} rows; the {nb}-branch step on {x.shape[0]} latents needs {nb * x.shape[0]}")
     if fused and x.is_cuda:
         from . import ops
         return ops.cfg_euler_step(x, eps, sigma, sigma_next, scale, scale_im)
+    if nb == 2:
+        e_u, e_c = eps.float().chunk(2)
+        du, dc = x - sigma * e_u, x - sigma * e_c
+        d0 = du + scale * (dc - du)
+        return x + (x - d0) / sigma * (sigma_next - sigma)
     e_u, e_ic, e_c = eps.float().chunk(3)
     den = [x - sigma * e for e in (e_u, e_ic, e_c)]
     d0 = den[0] + scale * (den[2] - den[1]) + scale_im * (den[1] - den[0])
     return x + (x - d0) / sigma * (sigma_next - sigma)
 
 
-def fused_cfg3_euler_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
-                          scale: float, scale_im: float, fused: bool = True) -> torch.Tensor:
-    """ONE step of EulerEDMSampler.sampler_step (sampling.py:85-136) under ScheduledCFGImgTextRef (guiders.py:102-133) and
-    DiscreteDenoiser + EpsScaling (denoiser.py:47-79), in the form the product's sampling job launches it (cd360/job.py):
+def guider_scales(guider):
+    """(scale, scale_im) as cfg_euler_update takes them: scale_im=None for the two-branch VanillaCFGImgRef."""
+    if isinstance(guider, ScheduledCFGImgTextRef):
+        return guider.scale, guider.scale_im
+    if isinstance(guider, VanillaCFGImgRef):
+        return guider.scale, None
+    raise TypeError(f"the fused step serves ScheduledCFGImgTextRef and VanillaCFGImgRef, not {type(guider).__name__}")
 
-        x3 = [x | x | x]                                   guider.prepare_inputs (the conditioning batch is assembled once per image)
-        x_in, c_noise = c_in(sigma_q) x3, idx(sigma_q)     DiscreteDenoiser.network_inputs, sigma snapped to the table ON the device
+
+def fused_cfg_euler_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
+                         guider, fused: bool = True) -> torch.Tensor:
+    """ONE step of EulerEDMSampler.sampler_step (sampling.py:85-136) under ScheduledCFGImgTextRef (guiders.py:102-133) or VanillaCFGImgRef
+    (guiders.py:136-166) and DiscreteDenoiser + EpsScaling (denoiser.py:47-79), in the form the product's sampling job launches it
+    (cd360/job.py); B = guider.branches:
+
+        xB = [x] * B                                       guider.prepare_inputs (the conditioning batch is assembled once per image)
+        x_in, c_noise = c_in(sigma_q) xB, idx(sigma_q)     DiscreteDenoiser.network_inputs, sigma snapped to the table ON the device
         eps = network(x_in, c_noise)                       the UNet over the CFG batch
-        x' = cfg_euler_update(x, eps, sigma, sigma_next)   c_out scaling + 3-way combine + to_d + Euler: cd360_cfg_euler_step_f32
+        x' = cfg_euler_update(x, eps, sigma, sigma_next)   c_out scaling + CFG combine + to_d + Euler: cd360_cfg_euler_step_f32
 
-    `network(x_in, c_noise) -> eps [3 n, ...]`; sigma / sigma_next 0-d device tensors of the sampler's schedule (table entries, so the
+    `network(x_in, c_noise) -> eps [B n, ...]`; sigma / sigma_next 0-d device tensors of the sampler's schedule (table entries, so the
     snapped sigma_q of c_out equals the sigma of to_d, as in the reference's own run).  No host synchronisation anywhere in the step."""
-    x3 = x.expand(3, *x.shape[1:]) if x.shape[0] == 1 else torch.cat([x] * 3)
-    x_in, c_noise, _, _, _ = denoiser.network_inputs(x3, sigma.expand(x3.shape[0]), {})
+    scale, scale_im = guider_scales(guider)
+    nb = guider.branches
+    xb = x.expand(nb, *x.shape[1:]) if x.shape[0] == 1 else torch.cat([x] * nb)
+    x_in, c_noise, _, _, _ = denoiser.network_inputs(xb, sigma.expand(xb.shape[0]), {})
     eps = network(x_in, c_noise)
     return cfg_euler_update(x, eps.contiguous(), sigma.reshape(1), sigma_next.reshape(1), scale, scale_im, fused=fused)
+
+
+def fused_cfg3_euler_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
+                          scale: float, scale_im: float, fused: bool = True) -> torch.Tensor:
+    """fused_cfg_euler_step under ScheduledCFGImgTextRef(scale, scale_im): the three-branch step by its earlier name."""
+    return fused_cfg_euler_step(denoiser, network, x, sigma, sigma_next, ScheduledCFGImgTextRef(scale, scale_im), fused=fused)

@@ -9,7 +9,7 @@ the (constant) text context are projected once per image instead of once per blo
 """
 from __future__ import annotations
 
-from typing import Iterable, List
+from typing import Iterable, List, Optional
 
 import torch
 
@@ -33,8 +33,22 @@ def set_references(model: torch.nn.Module, references: dict) -> None:
             blk.register_buffer("references", ref)
 
 
-def enable_reference_sampling(model: torch.nn.Module, choices: Iterable[int], cache_context: bool = True) -> List[str]:
+def set_cfg_branches(model: torch.nn.Module, branches: Optional[int]) -> None:
+    """State the CFG layout of the batches the pose blocks will see: `branches` x bs rows, the first bs of them unconditional (null image),
+    2 = VanillaCFGImgRef [uc | c], 3 = ScheduledCFGImgTextRef [uc | image | image+text].  None: the blocks infer it from `batch % 3` as
+    sample.py:89 does -- right for sample.py's one pose per call, wrong for two branches of three poses."""
+    if branches not in (None, 2, 3):
+        raise ValueError(f"branches must be None, 2 or 3, got {branches!r}")
+    for _, blk in pose_blocks(model):
+        if blk.cfg_branches != branches:
+            blk.cfg_branches = branches
+            blk.rendered_feat = None  # (a cached render was laid out for the other count)
+
+
+def enable_reference_sampling(model: torch.nn.Module, choices: Iterable[int], cache_context: bool = True,
+                              branches: Optional[int] = None) -> List[str]:
     """Switch every pose block to sample.py semantics with the given reference-view `choices` (sample.py:274-278).
+    `branches`: the CFG branch count of the batches to come (set_cfg_branches); cd360.job.Sampler states its guider's.
 
     cache_context=True additionally keeps the cross-attention K / V projections of the text context resident between steps.
     Contract: the `context` buffer handed to the UNet is not rewritten in place-without-version-bump or re-allocated until
@@ -47,6 +61,7 @@ def enable_reference_sampling(model: torch.nn.Module, choices: Iterable[int], ca
         blk.reference_choices = choices
         blk.rendered_feat = None
         names.append(name)
+    set_cfg_branches(model, branches)
     for att in _cross_attentions(model):
         att.cache_context_kv = bool(cache_context)
         att._kv_cache = None
@@ -57,6 +72,7 @@ def enable_reference_sampling(model: torch.nn.Module, choices: Iterable[int], ca
 def disable_reference_sampling(model: torch.nn.Module) -> None:
     for _, blk in pose_blocks(model):
         blk.reference_choices = None
+        blk.cfg_branches = None
         blk.rendered_feat = None
     for att in _cross_attentions(model):
         att.cache_context_kv = False

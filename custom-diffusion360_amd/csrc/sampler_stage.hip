@@ -12,6 +12,8 @@
 // The input convolution is computed ONCE per diffusion sample and written to its three CFG branches (their inputs are identical).
 #include "cd360_common.h"
 
+#include <cmath>
+
 namespace {
 
 constexpr int TP = 64;  // pixels of one image row per workgroup
@@ -88,17 +90,21 @@ __global__ __launch_bounds__(256) void unet_stage_in_kernel(const float* __restr
   }
 }
 
-// x [bs, 4, HW] fp32, updated IN PLACE; eps [3 bs, HW, ld] bf16 channels-last (channels 0..3 of each pixel row; u | ic | c thirds)
+// x [bs, 4, HW] fp32, updated IN PLACE; eps [NB bs, HW, ld] bf16 channels-last (channels 0..3 of each pixel row; NB = 3: u | ic | c thirds,
+// NB = 2: u | c halves -- no row past image 2 bs - 1 is read)
+template <int NB>
 __global__ __launch_bounds__(256) void cfg_euler_step_cl_kernel(float* __restrict__ x, const uint16_t* __restrict__ eps, const float* __restrict__ tab,
                                                                 const int* __restrict__ step, float scale, float scale_im, int bs, long HW, int ld) {
+  static_assert(NB == 2 || NB == 3, "two or three CFG branches");
   const int idx = *step;
   const float s = tab[idx * 4], sn = tab[idx * 4 + 1];
   const long total = (long)bs * HW;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const long smp = i / HW, px = i - smp * HW;
     const u32x2 eu = *reinterpret_cast<const u32x2*>(eps + ((0 * bs + smp) * HW + px) * ld);
-    const u32x2 ei = *reinterpret_cast<const u32x2*>(eps + ((1 * bs + smp) * HW + px) * ld);
-    const u32x2 ec = *reinterpret_cast<const u32x2*>(eps + ((2 * bs + smp) * HW + px) * ld);
+    u32x2 ei = eu;  // (NB = 2: unused)
+    if constexpr (NB == 3) ei = *reinterpret_cast<const u32x2*>(eps + ((1 * bs + smp) * HW + px) * ld);
+    const u32x2 ec = *reinterpret_cast<const u32x2*>(eps + (((NB - 1) * bs + smp) * HW + px) * ld);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const float e_u = (c & 1) ? bf16hi_to_f32(eu[c >> 1]) : bf16lo_to_f32(eu[c >> 1]);
@@ -106,8 +112,14 @@ __global__ __launch_bounds__(256) void cfg_euler_step_cl_kernel(float* __restric
       const float e_c = (c & 1) ? bf16hi_to_f32(ec[c >> 1]) : bf16lo_to_f32(ec[c >> 1]);
       float* xp = x + (smp * 4 + c) * HW + px;
       const float xv = *xp;
-      const float du = xv - s * e_u, dic = xv - s * e_i, dc = xv - s * e_c;  // (the arithmetic and its order: cfg_euler_step_kernel)
-      const float d0 = du + scale * (dc - dic) + scale_im * (dic - du);
+      float d0;  // (the arithmetic and its order: cfg_euler_step_kernel)
+      if constexpr (NB == 3) {
+        const float du = xv - s * e_u, dic = xv - s * e_i, dc = xv - s * e_c;
+        d0 = du + scale * (dc - dic) + scale_im * (dic - du);
+      } else {
+        const float du = xv - s * e_u, dc = xv - s * e_c;
+        d0 = du + scale * (dc - du);
+      }
       *xp = xv + (xv - d0) / s * (sn - s);
     }
   }
@@ -133,14 +145,19 @@ extern "C" int cd360_unet_stage_in(const void* x, const void* step_tab, const vo
   return CD360_OK;
 }
 
-// x [bs, 4, HW] fp32 in place; eps [3 bs, HW, ld] bf16 (ld >= 4, ld % 4 == 0: the 320 -> 4 output convolution writes 16-channel rows)
+// x [bs, 4, HW] fp32 in place; eps [3 bs, HW, ld] bf16 (ld >= 4, ld % 4 == 0: the 320 -> 4 output convolution writes 16-channel rows), or
+// eps [2 bs, HW, ld] when scale_im is NaN (tested here, on the host: the kernel never sees it)
 extern "C" int cd360_cfg_euler_step_cl(void* x, const void* eps, const void* step_tab, const void* step, float scale, float scale_im, int bs,
                                        int64_t HW, int ld, void* stream) {
   if (!x || !eps || !step_tab || !step || bs <= 0 || HW <= 0 || ld < 4 || ld % 4) return CD360_ERR_ARG;
   if ((uintptr_t)eps % 8) return CD360_ERR_ARG;
   const long total = (long)bs * HW;
-  hipLaunchKernelGGL(cfg_euler_step_cl_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (float*)x,
-                     (const uint16_t*)eps, (const float*)step_tab, (const int*)step, scale, scale_im, bs, (long)HW, ld);
+  if (std::isnan(scale_im))
+    hipLaunchKernelGGL(cfg_euler_step_cl_kernel<2>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (float*)x,
+                       (const uint16_t*)eps, (const float*)step_tab, (const int*)step, scale, 0.f, bs, (long)HW, ld);
+  else
+    hipLaunchKernelGGL(cfg_euler_step_cl_kernel<3>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (float*)x,
+                       (const uint16_t*)eps, (const float*)step_tab, (const int*)step, scale, scale_im, bs, (long)HW, ld);
   CD360_LAUNCH_CHECK();
   return CD360_OK;
 }

@@ -398,6 +398,7 @@ class BasicTransformerBlock(nn.Module):
         self.use_prev_weights_imp_sample, self.imp_sample_next_step = use_prev_weights_imp_sample, imp_sample_next_step
         self.rendered_feat = None
         self.reference_choices = None  # set by cd360.sampling.enable_reference_sampling (native sample.py mode)
+        self.cfg_branches = None  # stated CFG branch count of the sampling batches (cd360.sampling.set_cfg_branches); None: inferred, % 3
         attn_cls = self.ATTENTION_MODES[attn_mode]
         self.disable_self_attn = disable_self_attn
         self.attn1 = attn_cls(query_dim=dim, heads=n_heads, dim_head=d_head, dropout=dropout, add_lora=add_lora, context_dim=None,
@@ -543,7 +544,7 @@ class BasicTransformerBlock(nn.Module):
         nerf = self.pose_featurenerf
         if self.use_prev_weights_imp_sample and (prev_weights is not None or (self.imp_sample_next_step and nerf.honour_imp_sample_next_step)):
             return self._reference_attn_importance(x, context_ref, context, pose, prev_weights, mask_ref, tables, dims)
-        dup = self._duplicate_cfg_branch(pose, dims) if (tables is not None and context_ref is None and mask_ref is None) else 0
+        dup = self._duplicate_cfg_branch(pose, dims, self.cfg_branches) if (tables is not None and context_ref is None and mask_ref is None) else 0
         if dup:
             # 3-way CFG (guiders.py:102-133): the image-conditional and the image+text-conditional thirds see the same target
             # pose and the same references, so everything BEFORE the text cross-attention is identical for them: render the
@@ -619,10 +620,11 @@ class BasicTransformerBlock(nn.Module):
         return rendered, fg, (None if not self.use_prev_weights_imp_sample else None), alphas, rgb
 
     @staticmethod
-    def _duplicate_cfg_branch(pose, dims) -> int:
+    def _duplicate_cfg_branch(pose, dims, branches=None) -> int:
         """bs > 0 when `pose` is a list of 3*bs camera batches whose last two thirds are the SAME objects (what the guider's
-        `[pose] * 3` / torch.cat of one conditioning produces); decided on object identity only -- no device comparison."""
-        if routes.no_cfg_dedup or not isinstance(pose, (list, tuple)) or dims is None:
+        `[pose] * 3` / torch.cat of one conditioning produces); decided on object identity only -- no device comparison.
+        A stated two-branch layout has no duplicate branch, whatever its row count."""
+        if routes.no_cfg_dedup or not isinstance(pose, (list, tuple)) or dims is None or branches not in (None, 3):
             return 0
         b = len(pose)
         if b != dims[0] or b % 3:
@@ -636,6 +638,10 @@ class BasicTransformerBlock(nn.Module):
         refs, choices = self.references, self.reference_choices
         sel = refs[:-1][torch.as_tensor(choices, device=refs.device)]  # [n, hw, C]
         n = sel.shape[0]
+        if self.cfg_branches is not None:  # stated: [null x bs | references x bs (| references x bs)]
+            bs = self._cfg_layout(batch_size, self.cfg_branches)[0]
+            cond = sel[None].expand(bs, -1, -1, -1)
+            return torch.cat([refs[-1:][None].expand(bs, n, -1, -1)] + [cond] * (self.cfg_branches - 1), 0)
         if batch_size % 3 == 0:
             bs = batch_size // 3
             cond = sel[None].expand(bs, -1, -1, -1)
@@ -645,8 +651,13 @@ class BasicTransformerBlock(nn.Module):
         return torch.cat([refs[-1:][None].expand(bs, n, -1, -1), cond], 0)
 
     @staticmethod
-    def _cfg_layout(batch_size: int):
-        """(n_null, n_cond) of sample.py's CFG batch (sample.py:89-96): the first third (3-way) or half (2-way) is unconditional."""
+    def _cfg_layout(batch_size: int, branches=None):
+        """(n_null, n_cond) of sample.py's CFG batch (sample.py:89-96): the first third (3-way) or half (2-way) is unconditional.
+        `branches` states which; None infers it from the batch size as sample.py:89 does."""
+        if branches is not None:
+            if batch_size % branches:
+                raise ValueError(f"a batch of {batch_size} rows is not {branches} CFG branches of whole samples")
+            return batch_size // branches, batch_size - batch_size // branches
         if batch_size % 3 == 0:
             return batch_size // 3, 2 * (batch_size // 3)
         return batch_size // 2, batch_size - batch_size // 2
@@ -782,7 +793,7 @@ class BasicTransformerBlock(nn.Module):
             if self.reference_choices is not None:  # native equivalent of sample.py's _customforward (sample.py:82-136)
                 if self.rendered_feat is None:
                     if mask_ref is None:  # tables of the DISTINCT reference images, kept across images / poses
-                        tables, dims = self._sampling_tables(*self._cfg_layout(x.size(0)))
+                        tables, dims = self._sampling_tables(*self._cfg_layout(x.size(0), self.cfg_branches))
                         xref, fg_mask, weights, alphas, predicted_rgb = self.reference_attn(x, None, context, pose, prev_weights, None,
                                                                                             tables=tables, dims=dims)
                     else:
@@ -850,7 +861,7 @@ class BasicTransformerBlock(nn.Module):
             if self.reference_choices is not None:  # native equivalent of sample.py's _customforward (sample.py:82-136)
                 if self.rendered_feat is None:
                     if mask_ref is None:  # tables of the DISTINCT reference images, kept across images / poses
-                        tables, dims = self._sampling_tables(*self._cfg_layout(x.size(0)))
+                        tables, dims = self._sampling_tables(*self._cfg_layout(x.size(0), self.cfg_branches))
                         xref, fg_mask, weights, alphas, predicted_rgb = self.reference_attn(x, None, context, pose, prev_weights, None,
                                                                                             tables=tables, dims=dims)
                     else:

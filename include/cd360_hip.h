@@ -360,7 +360,13 @@ int cd360_add_layernorm_bwd_bf16(const void* x, const void* gamma, const void* d
 
 /* replaces the elementwise tail of one sampling step: DiscreteDenoiser's c_out/c_skip (denoiser.py:41-44), ScheduledCFGImgTextRef.__call__
  * (guiders.py:111-114), to_d and the Euler update (sampling.py:101-106).  x [n] fp32, eps [3n] fp32 (u | ic | c), sigma / sigma_next
- * device scalars; out [n] = x + (x - d0)/sigma * (sigma_next - sigma), d0 = den_u + scale (den_c - den_ic) + scale_im (den_ic - den_u). */
+ * device scalars; out [n] = x + (x - d0)/sigma * (sigma_next - sigma), d0 = den_u + scale (den_c - den_ic) + scale_im (den_ic - den_u).
+ * Two branches (VanillaCFGImgRef.__call__, guiders.py:144-147): a NaN scale_im selects eps [2n] fp32 (u | c) and
+ * d0 = den_u + scale (den_c - den_u), the expression above without its image term, same order; nothing behind eps[2n - 1] is read.  The NaN is
+ * tested on the host before the launch and never reaches the kernel.  It is the signal because it adds no symbol and changes no signature,
+ * and no working call changes meaning: a NaN scale_im used to give an all-NaN latent.  Zero and negative scale_im stay three-branch calls
+ * with their arithmetic as it was (whether "scale_im <= 0" MEANS two branches, as in sample.py:231-240, is the caller's decision:
+ * cd360/job.py::Sampler makes it and passes the NaN). */
 int cd360_cfg_euler_step_f32(const void* x, const void* eps, const void* sigma, const void* sigma_next, float scale, float scale_im,
                              void* out, int64_t n, void* stream);
 
@@ -373,7 +379,9 @@ int cd360_cfg_euler_step_f32(const void* x, const void* eps, const void* sigma, 
  *   (channels-last; the `rep` CFG branches of a sample get identical rows); temb_tab [nsteps, E] bf16 = time_embed(timestep_embedding(c_noise))
  *   per step; lab [rep * bs, E] bf16 = label_emb(y); emb_act [rep * bs, E] bf16 out = silu(temb_tab[step] + lab).
  * cd360_cfg_euler_step_cl: cd360_cfg_euler_step_f32's arithmetic on x [bs, 4, HW] fp32 IN PLACE with eps [3 bs, HW, ld] bf16 channels-last
- *   (channels 0..3 of every ld-wide row: the 320 -> 4 output convolution's padded rows), sigma / sigma_next = step_tab[step][0 / 1]. */
+ *   (channels 0..3 of every ld-wide row: the 320 -> 4 output convolution's padded rows), sigma / sigma_next = step_tab[step][0 / 1].
+ *   A NaN scale_im selects the two-branch form exactly as for cd360_cfg_euler_step_f32: eps [2 bs, HW, ld] (u | c images), no row of a
+ *   third branch read.  (cd360_unet_stage_in feeds it with rep = 2.) */
 int cd360_unet_stage_in(const void* x, const void* step_tab, const void* step, const void* w_k36, const void* bias, void* h, const void* temb_tab,
                         const void* lab, void* emb_act, int bs, int rep, int H, int W, int Cout, int E, void* stream);
 int cd360_cfg_euler_step_cl(void* x, const void* eps, const void* step_tab, const void* step, float scale, float scale_im, int bs, int64_t HW,
