@@ -55,12 +55,25 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const uint16_t* __restr
 // grid (G, N): one workgroup reduces the nslab x cpg x (sum, sumsq) partials of one group -- every thread a fixed stride of them with
 // four independent loads in flight, an xor tree inside each wave, the four wave sums through the LDS in a fixed order: deterministic, ONE
 // workgroup barrier (the eight-barrier LDS tree of rounds 1-5 was most of this kernel's 6 us: 46 launches per denoise step).
+// The partials are RAW sums, and var = E[x^2] - mean^2 over the whole group loses log2(1 + (mean / std)^2) of fp32's 24 bits: a tenth
+// of the variance is gone at |mean| / std ~ 100, which the first stage's GroupNorms reach.  So the same pass also forms the CENTRED
+// statistics: each item (slab, channel) of n_i pixels is turned into (n_i, mean_i, M2_i = ss_i - s_i mean_i), where only that slab's few
+// pixels cancel, and the items are merged by Chan's update of (count, mean, M2), written for all parts at once about one pivot c (the
+// first item's mean, the same in every thread):
+//   with d_i = mean_i - c:   sum_i n_i d_i = n (mean - c),   sum_i (M2_i + n_i d_i^2) = M2 + n (mean - c)^2,
+// plain sums again, so the reduction keeps its fixed order and its one barrier.  c lies inside the group's data, so (mean - c)^2 is of
+// the order of the variance and the last subtraction is benign.  Thread 0 keeps the raw pair while it is well conditioned, mean^2 <=
+// GN_RAW_MAX_RATIO2 * var (at most 6 bits lost, and activations normalised so far keep their bits), and takes the centred pair beyond.
+constexpr float GN_RAW_MAX_RATIO2 = 64.f;  // (|mean| / std)^2 up to which the raw sums decide
+
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ partial, float* __restrict__ stat, int P, int C, int G,
                                                           float eps, int nslab) {
-  __shared__ float red[8];
+  __shared__ float red[16];
   const int g = blockIdx.x, n = blockIdx.y, cpg = C / G, tid = threadIdx.x, lane = tid & 63, items = nslab * cpg;
   const f32x2* src = reinterpret_cast<const f32x2*>(partial) + (long)n * nslab * C + g * cpg;
-  float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
+  float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f}, cs[4] = {0.f, 0.f, 0.f, 0.f}, cq[4] = {0.f, 0.f, 0.f, 0.f};
+  const int even = P % nslab ? 0 : P / nslab;  // pixels per slab when the slabs are equal (every producer's: P % nslab == 0)
+  const float pivot = src[0][0] / (float)(P / nslab);
   for (int i0 = tid; i0 < items; i0 += 1024) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -68,27 +81,42 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
       if (i < items) {
         const int sl = i / cpg;
         const f32x2 v = src[(long)sl * C + (i - sl * cpg)];
+        const float ni = (float)(even ? even : (int)((long)P * (sl + 1) / nslab) - (int)((long)P * sl / nslab));  // gn_partial_kernel's p1 - p0
+        const float mi = v[0] / ni, d = mi - pivot;
         s[u] += v[0];
         ss[u] += v[1];
+        cs[u] = fmaf(ni, d, cs[u]);
+        cq[u] += fmaxf(fmaf(-v[0], mi, v[1]), 0.f) + ni * d * d;
       }
     }
   }
   float a = (s[0] + s[1]) + (s[2] + s[3]), b = (ss[0] + ss[1]) + (ss[2] + ss[3]);
+  float ca = (cs[0] + cs[1]) + (cs[2] + cs[3]), cb = (cq[0] + cq[1]) + (cq[2] + cq[3]);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     a += __shfl_xor(a, o);
     b += __shfl_xor(b, o);
+    ca += __shfl_xor(ca, o);
+    cb += __shfl_xor(cb, o);
   }
   if (lane == 0) {
     red[2 * (tid >> 6)] = a;
     red[2 * (tid >> 6) + 1] = b;
+    red[8 + 2 * (tid >> 6)] = ca;
+    red[8 + 2 * (tid >> 6) + 1] = cb;
   }
   __syncthreads();
   if (tid == 0) {
     const float sum = (red[0] + red[2]) + (red[4] + red[6]), sq = (red[1] + red[3]) + (red[5] + red[7]);
+    const float csum = (red[8] + red[10]) + (red[12] + red[14]), csq = (red[9] + red[11]) + (red[13] + red[15]);
     const float cnt = (float)cpg * (float)P;
-    const float mean = sum / cnt;
-    const float var = fmaxf(sq / cnt - mean * mean, 0.f);
+    float mean = sum / cnt;
+    float var = fmaxf(sq / cnt - mean * mean, 0.f);
+    if (mean * mean > GN_RAW_MAX_RATIO2 * var) {
+      const float dm = csum / cnt;  // mean - pivot
+      var = fmaxf(csq / cnt - dm * dm, 0.f);
+      mean = pivot + dm;
+    }
     stat[((long)n * G + g) * 2] = mean;
     stat[((long)n * G + g) * 2 + 1] = 1.f / sqrtf(var + eps);
   }
@@ -149,6 +177,7 @@ extern "C" int cd360_gn_silu_bf16(const void* x, const void* gamma, const void* 
   if (!x || !gamma || !beta || !y || !ws || N <= 0 || P <= 0 || C <= 0 || G <= 0) return CD360_ERR_ARG;
   if (C % 8 || C % G || C > MAX_C || G > 64) return CD360_ERR_SHAPE;
   if (tile_stats && stats_slabs <= 0) return CD360_ERR_ARG;
+  if (tile_stats && P % stats_slabs) return CD360_ERR_SHAPE;  // equal slabs: gn_finalize_kernel needs every slab's pixel count
   const int nslab = tile_stats ? stats_slabs : gn_num_slabs(P);
   float* partial = tile_stats ? (float*)tile_stats : (float*)ws;
   float* stat = (float*)ws + (long)N * gn_num_slabs(P) * 2 * C;

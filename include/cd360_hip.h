@@ -329,7 +329,8 @@ int64_t cd360_gn_workspace_bytes(int N, int P, int C);
 int cd360_gn_silu_bf16(const void* x, const void* gamma, const void* beta, void* y, void* ws, int N, int P, int C, int G, float eps,
                        int silu, const void* tile_stats, int stats_slabs, void* stream);
 /* tile_stats / stats_slabs (optional, NULL / 0): per-slab channel sums [N, stats_slabs, C, 2] already produced by the conv that
- * wrote x (cd360_conv_igemm_bf16); the statistics read pass over x is then skipped. */
+ * wrote x (cd360_conv_igemm_bf16); the statistics read pass over x is then skipped.  The slabs are equal, P / stats_slabs consecutive
+ * pixels each (the merge needs every slab's pixel count): P % stats_slabs != 0 is CD360_ERR_SHAPE. */
 
 /* Backward of cd360_gn_silu_bf16 with respect to x (GroupNorm32 / SiLU under torch autograd in the reference's training loop):
  * x, dy, dx [N, P, C] bf16 (dx may alias dy); ws = cd360_gn_bwd_workspace_bytes(N, P, C) bytes.  No gamma / beta gradients. */
