@@ -61,24 +61,35 @@ __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* T, int db, int kk
   return __builtin_bit_cast(bf16x8, v);
 }
 
-// delta[bh, row] = sum_d dO * O   (one 8-lane group per row: 16-byte pieces of full 128-byte lines)
+// delta[bh, row] = sum_d dO * O   (one 8-lane group per row: 16-byte pieces of full 128-byte lines).  Summed in the order of the delta
+// fused into the dQ role below -- two running sums over the 16-byte pieces 0, 2, 4, 6 and 1, 3, 5, 7, then their sum -- so that dk / dv of
+// the dk/dv-only launch equal, bit for bit, those of the launch that follows a dQ role.
 __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(const uint16_t* o, const uint16_t* dout, float* delta, int H, int Nq, long o_sb,
                                                              long o_sh, long o_sn, long do_sb, long do_sh, long do_sn, long rows) {
   const long gid = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
   const int chunk = threadIdx.x & 7;
-  float acc = 0.f;
+  float term[4] = {0.f, 0.f, 0.f, 0.f};
   if (gid < rows) {
     const long bh = gid / Nq, r = gid - bh * Nq;
     const long b = bh / H, h = bh - b * H;
     const u32x4 a = *reinterpret_cast<const u32x4*>(o + b * o_sb + h * o_sh + r * o_sn + chunk * 8);
     const u32x4 g = *reinterpret_cast<const u32x4*>(dout + b * do_sb + h * do_sh + r * do_sn + chunk * 8);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) acc += bf16lo_to_f32(a[i]) * bf16lo_to_f32(g[i]) + bf16hi_to_f32(a[i]) * bf16hi_to_f32(g[i]);
+    for (int i = 0; i < 4; ++i) term[i] = bf16lo_to_f32(a[i]) * bf16lo_to_f32(g[i]) + bf16hi_to_f32(a[i]) * bf16hi_to_f32(g[i]);
   }
-  acc += __shfl_xor(acc, 1);
-  acc += __shfl_xor(acc, 2);
-  acc += __shfl_xor(acc, 4);
-  if (gid < rows && chunk == 0) delta[gid] = acc;
+  float acc = 0.f;
+#pragma unroll
+  for (int stage = 0; stage < 4; ++stage) {  // piece c continues the running sum of piece c - 2
+    const float in = __shfl_up(acc, 2);
+    if ((chunk >> 1) == stage) {
+      float s = stage ? in : 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s += term[i];
+      acc = s;
+    }
+  }
+  acc += __shfl_xor(acc, 1);  // lanes 6 | 7 of the group: even pieces + odd pieces
+  if (gid < rows && chunk == 6) delta[gid] = acc;
 }
 
 template <bool DKV>

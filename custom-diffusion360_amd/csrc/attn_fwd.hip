@@ -396,7 +396,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_self_kernel(Att
   };
 
   const int n_tiles = p.Nk / BN;
-  // tile maximum of one query block (this lane's column; both key halves through lane ^ 32)
+  // tile maxima of one query block (this lane's column): .ref = over the key rows held by lanes 0-31 (rows 0-3, 8-11, ... of each 32-key
+  // block), .all = over both key halves.
+  struct TileMax { float ref, all; };
   auto tile_max = [&](const f32x16 (&s)[2]) {
     float m[4];
 #pragma unroll
@@ -408,9 +410,17 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_self_kernel(Att
     }
     const float ma = fmaxf(fmaxf(m[0], m[1]), s[0][7]), mb = fmaxf(fmaxf(m[2], m[3]), s[0][15]);
     const float mx = fmaxf(fmaxf(ma, mb), fmaxf(s[1][7], s[1][15]));
-    // both key halves: v_permlane32_swap (VALU) instead of a ds_bpermute round trip on the way to the end-of-tile branch
-    const auto sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, mx), __builtin_bit_cast(unsigned, mx), false, false);
-    return fmaxf(__builtin_bit_cast(float, sw[0]), __builtin_bit_cast(float, sw[1]));
+    // both key halves: v_permlane32_swap (VALU) instead of a ds_bpermute round trip on the way to the end-of-tile branch: lanes 32-63 of the
+    // first register trade places with lanes 0-31 of the second, so one holds the lower half's maximum in every lane and the other the
+    // upper half's.  Written as inline asm: through __builtin_amdgcn_permlane32_swap this compiler reads the FIRST result for both
+    // (v_max_f32 v, v_first, v_first), so every lane kept the maximum of lanes 0-31 alone; a dominating key in the other half never moved
+    // m_ref, and more than 128 units above it exp2 overflowed (inf in l, NaN in O).
+    // (s_nop 1: the two wait states between the VALU writes above and this instruction's reads, which the compiler no longer counts.)
+    // m_ref still FOLLOWS .ref, as it always has: where the other half stays within the slack nothing changes, not even a rounding (every
+    // result the kernel gave without overflowing stays bit for bit).  What .all adds is catch_up below.
+    float lo = mx, hi = mx;
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lo), "+v"(hi));
+    return TileMax{lo, fmaxf(lo, hi)};
   };
   // the rare path: move m_ref of query block qb by d (>= 0 except on the first tile) and rescale what hangs on it
   auto move_ref = [&](int qb, float d, f32x16 (&s)[2]) {
@@ -422,6 +432,22 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_self_kernel(Att
     for (int i = 0; i < 16; ++i) {
       negm[qb][i] -= d;
       s[0][i] -= d; s[1][i] -= d;
+      oT[qb][0][i] *= alpha; oT[qb][1][i] *= alpha;
+    }
+  };
+  // the rarer path: after m_ref has followed .ref (by d), the other key half may still stand more than the slack above it.  m_ref then
+  // moves on by a WHOLE number of units: l, O and every p scale by an exact power of two, so which tile this happens at leaves no trace
+  // in the roundings of P.
+  auto catch_up = [&](int qb, const TileMax& tm, float d, f32x16 (&s)[2]) {
+    const float rest = tm.all - d;
+    const float n = rest > 8.f ? floorf(rest) : 0.f;
+    if (__builtin_amdgcn_ballot_w64(n > 0.f) == 0) return;
+    const float alpha = ldexpf(1.f, -(int)n);
+    l_run[qb] *= alpha;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      negm[qb][i] -= n;
+      s[0][i] -= n; s[1][i] -= n;
       oT[qb][0][i] *= alpha; oT[qb][1][i] *= alpha;
     }
   };
@@ -472,12 +498,16 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_self_kernel(Att
     __syncthreads();
     qk(lds, sc);
 #pragma unroll
-    for (int qb = 0; qb < QB; ++qb) move_ref(qb, tile_max(sc[qb]), sc[qb]);
+    for (int qb = 0; qb < QB; ++qb) {
+      const TileMax tm = tile_max(sc[qb]);
+      move_ref(qb, tm.ref, sc[qb]);
+      catch_up(qb, tm, tm.ref, sc[qb]);
+    }
     // steady state, ONE basic block per tile: S' MFMAs of tile t+1 | exp / sum / pack of tile t | P V MFMAs of tile t | max of t+1
     for (int t = 0; t + 1 < n_tiles; ++t) {
       rendezvous(t, t + 1);
       uint32_t pk[QB][16];
-      float mx[QB];
+      TileMax mx[QB];
       qk(lds + ((t + 1) % NB) * TILE_BYTES, sn);
 #pragma unroll
       for (int qb = 0; qb < QB; ++qb) softmax_p(qb, sc[qb], pk[qb]);
@@ -486,11 +516,15 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_self_kernel(Att
 #pragma unroll
       for (int qb = 0; qb < QB; ++qb) {
         mx[qb] = tile_max(sn[qb]);
-        any = any || mx[qb] > 8.f;
+        any = any || mx[qb].all > 8.f;  // (.all >= .ref)
       }
       if (__builtin_amdgcn_ballot_w64(any) != 0) {
 #pragma unroll
-        for (int qb = 0; qb < QB; ++qb) move_ref(qb, mx[qb] > 8.f ? mx[qb] : 0.f, sn[qb]);
+        for (int qb = 0; qb < QB; ++qb) {
+          const float d = mx[qb].ref > 8.f ? mx[qb].ref : 0.f;
+          move_ref(qb, d, sn[qb]);
+          catch_up(qb, mx[qb], d, sn[qb]);
+        }
       }
 #pragma unroll
       for (int qb = 0; qb < QB; ++qb) { sc[qb][0] = sn[qb][0]; sc[qb][1] = sn[qb][1]; }
@@ -511,8 +545,12 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_self_kernel(Att
       qk(Tc, sc);
 #pragma unroll
       for (int qb = 0; qb < QB; ++qb) {
-        const float mx = tile_max(sc[qb]);
-        if (__builtin_amdgcn_ballot_w64(t == 0 || mx > 8.f) != 0) move_ref(qb, (t == 0 || mx > 8.f) ? mx : 0.f, sc[qb]);
+        const TileMax mx = tile_max(sc[qb]);
+        if (__builtin_amdgcn_ballot_w64(t == 0 || mx.all > 8.f) != 0) {
+          const float d = (t == 0 || mx.ref > 8.f) ? mx.ref : 0.f;
+          move_ref(qb, d, sc[qb]);
+          catch_up(qb, mx, d, sc[qb]);
+        }
         softmax_p(qb, sc[qb], pk[qb]);
       }
       pv(Tc, pk);
