@@ -23,10 +23,18 @@ class Sampler:
     sample.py:231-240.  B = guider.branches: `ctx` / `y` hold B bs rows ([uc x bs | . | c x bs] resp. [uc x bs | c x bs]), `pose` B bs camera
     batches, and the UNet runs on B bs images (two branches: a third less work per step, not a duplicated branch).
     With `use_graph` the steady-state step (cached render) and the render step are each captured once into a hipGraph and
-    replayed: ~3000 launches per step are then issued by the GPU front end instead of the Python interpreter."""
+    replayed: ~3000 launches per step are then issued by the GPU front end instead of the Python interpreter.
+    `solver`: "euler" (EulerEDMSampler, sampling.py:85-136) or "dpmpp2m" (DPMPP2MSampler, sampling.py:390-465: second order, multistep,
+    the same one UNet evaluation per step); the step's tail kernel is the only difference.  DPM++ 2M carries the previous step's denoised
+    latent in `self.gd`, so `step(x, i)` for i > 0 must follow `step(., i - 1)` of the SAME image (`eps()` is unaffected)."""
 
-    def __init__(self, net, pose, ctx, y, n_steps, scale=7.5, scale_im=3.5, use_graph=False, prefetch=None, graph_render=True):
+    SOLVERS = ("euler", "dpmpp2m")
+
+    def __init__(self, net, pose, ctx, y, n_steps, scale=7.5, scale_im=3.5, use_graph=False, prefetch=None, graph_render=True, solver="euler"):
         from cd360 import sampler as S
+        if solver not in self.SOLVERS:
+            raise ValueError(f"solver {solver!r}: the job sampler serves {' and '.join(self.SOLVERS)}")
+        self.solver = solver
         self.net, self.pose, self.n_steps = net, pose, n_steps
         if use_graph:  # the graphs read the cameras through ONE buffer this sampler owns (retarget rewrites it in place)
             from sgm.modules.utils_cameraray import PoseBuffer
@@ -121,6 +129,18 @@ class Sampler:
         nbs, (H, W) = self.y.shape[0], x.shape[2:]  # B bs images
         self.h0 = torch.empty(nbs, H * W, conv.out_channels, dtype=dt, device=dev)
         self.emb_act = torch.empty_like(self.lab)
+        if self.solver == "dpmpp2m":
+            self._build_solver(x)
+
+    def _build_solver(self, x):
+        """DPM++ 2M state: the multiplier table (host fp32, uploaded: the same bits in every sampler of a schedule), the un-staged step's
+        4-float row buffer, and gd = the previous step's denoised latent d0, shaped like gx and shared by both captured graphs.  retarget()
+        does not reset gd: row 0 of the table has m4 = 0 and the kernels then never read it -- which is also why step(x, i) for i > 0 must
+        follow step(., i - 1) of the same image."""
+        from cd360.sampler import dpmpp2m_multipliers
+        self.mult_tab = dpmpp2m_multipliers(self.sigmas).to(x.device)
+        self.gm = self.mult_tab[0].clone()
+        self.gd = torch.zeros_like(x)
 
     def _math_staged(self):
         """One sampler step on the static buffers, in place on self.gx: stage-in kernel (rep = B) -> UNet trunk -> fused [c_out, CFG, to_d,
@@ -129,13 +149,20 @@ class Sampler:
         H, W = self.gx.shape[2:]
         ops.unet_stage_in(self.gx, self.step_tab, self.gi, self.w36, self.b_in, self.temb_tab, self.lab, self.h0, self.emb_act)
         eps_cl = self.net.forward_staged(self.h0, self.emb_act, self.ctx, self.pose, H, W)
+        if self.solver == "dpmpp2m":  # x and gd in place: [c_out, CFG, multistep update]
+            return ops.cfg_dpmpp2m_step_cl(self.gx, self.gd, eps_cl, self.step_tab, self.mult_tab, self.gi, self.scale, self.scale_im)
         return ops.cfg_euler_step_cl(self.gx, eps_cl, self.step_tab, self.gi, self.scale, self.scale_im)
 
     def _math(self, x, s, s_next, t_unused=None):
         """One sampler step = guider.prepare_inputs -> DiscreteDenoiser (sigma -> table index, c_in) -> UNet -> fused
-        [c_out, CFG, to_d, Euler] kernel."""
-        from cd360.sampler import fused_cfg_euler_step
+        [c_out, CFG, to_d, Euler] kernel -- or, for DPM++ 2M, the [c_out, CFG, multistep update] kernel on the row in self.gm, which also
+        moves this step's d0 into self.gd."""
+        from cd360.sampler import fused_cfg_dpmpp2m_step, fused_cfg_euler_step
         unet = lambda x_in, c_noise: self.net(x_in, timesteps=c_noise, context=self.ctx, y=self.y, pose=self.pose)[0]  # noqa: E731
+        if self.solver == "dpmpp2m":
+            out, d0 = fused_cfg_dpmpp2m_step(self.denoiser, unet, x, self.gd, s, self.gm, self.guider)
+            self.gd.copy_(d0)
+            return out
         return fused_cfg_euler_step(self.denoiser, unet, x, s, s_next, self.guider)
 
     @torch.no_grad()
@@ -214,6 +241,8 @@ class Sampler:
         self.gx, self.gs, self.gt = x.clone(), torch.stack([s, s_next]), t.clone()
         if self.staged:
             self._build_stage(x)
+        elif self.solver == "dpmpp2m":
+            self._build_solver(x)
         self._render()
         if self.staged:
             self.gx.copy_(x)  # (the staged step updates gx in place: captures and warm-ups below start from a sane latent again)
@@ -276,9 +305,15 @@ class Sampler:
                 from cd360 import sampling
                 sampling.clear_rendered_feat(self.net)  # new image: the render runs again
                 self._state_layout()
+            if self.solver == "dpmpp2m":
+                if getattr(self, "mult_tab", None) is None:
+                    self._build_solver(x)
+                self.gm.copy_(self.mult_tab[i])
             return self._math(x, s, s_next, t)
         self.prepare(x)
         self.gx.copy_(x)
+        if self.solver == "dpmpp2m":
+            self.gm.copy_(self.mult_tab[i])
         self.gs[0].copy_(s)
         self.gs[1].copy_(s_next)
         self.gt.copy_(t)

@@ -1271,6 +1271,48 @@ def cfg_euler_step_cl(x: torch.Tensor, eps_cl: torch.Tensor, step_tab: torch.Ten
     return x
 
 
+def cfg_dpmpp2m_step(x: torch.Tensor, eps: torch.Tensor, old: torch.Tensor, sigma: torch.Tensor, mult: torch.Tensor, scale: float,
+                     scale_im: Optional[float]):
+    """One DPM++ 2M tail (cd360_cfg_dpmpp2m_step_f32, include/cd360_solvers.h): x, old [n,...] fp32, eps [3n,...] fp32 (u | ic | c) or, with
+    scale_im=None, [2n,...] (u | c), sigma a 1-element and mult = (m1, m2, m3, m4) a 4-element fp32 device tensor -> (x', d0), both new
+    tensors.  `old` is not read when m4 == 0."""
+    _need_gpu(x, eps, old, sigma, mult)
+    nb = _cfg_branches(scale_im)
+    if eps.shape[0] != nb * x.shape[0] or eps.numel() != nb * x.numel():
+        raise ValueError(f"eps holds {eps.shape[0]} rows of {tuple(eps.shape[1:])}; the {nb}-branch step on x {tuple(x.shape)} needs {nb * x.shape[0]}")
+    assert x.dtype == torch.float32 and eps.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
+    assert old.dtype == torch.float32 and old.shape == x.shape and old.is_contiguous()
+    assert sigma.dtype == torch.float32 and sigma.numel() == 1 and mult.dtype == torch.float32 and mult.numel() == 4 and mult.is_contiguous()
+    out, old_out = torch.empty_like(x), torch.empty_like(x)
+    check(_lib.load().cd360_cfg_dpmpp2m_step_f32(_ptr(x), _ptr(eps), _ptr(old), _ptr(sigma), _ptr(mult), float(scale),
+                                                float("nan") if nb == 2 else float(scale_im), _ptr(out), _ptr(old_out), x.numel(), _stream()),
+          "cd360_cfg_dpmpp2m_step_f32")
+    return out, old_out
+
+
+def cfg_dpmpp2m_step_cl(x: torch.Tensor, old: torch.Tensor, eps_cl: torch.Tensor, step_tab: torch.Tensor, mult_tab: torch.Tensor,
+                        step: torch.Tensor, scale: float, scale_im: Optional[float]):
+    """DPM++ 2M tail of a captured sampling step, IN PLACE on x and old [bs, 4, H, W] fp32 (cd360_cfg_dpmpp2m_step_cl): eps_cl as for
+    cfg_euler_step_cl, sigma = step_tab[step][0], (m1, m2, m3, m4) = mult_tab[step]; x <- m1 x - m2 dd, old <- d0.  `old` is not read
+    when m4 == 0."""
+    _need_gpu(x, old, eps_cl, step_tab, mult_tab, step)
+    nb = _cfg_branches(scale_im)
+    bs = x.shape[0]
+    hw = x.shape[2] * x.shape[3]
+    if eps_cl.shape[0] != nb * bs:
+        raise ValueError(f"eps_cl holds {eps_cl.shape[0]} images; the {nb}-branch step on {bs} latents needs {nb * bs}")
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == 4 and eps_cl.dtype == torch.bfloat16
+    assert old.dtype == torch.float32 and old.shape == x.shape and old.is_contiguous()
+    assert eps_cl.shape[1] == hw and eps_cl.shape[2] >= 4 and eps_cl.stride(2) == 1
+    assert step.dtype == torch.int32 and step_tab.dtype == torch.float32 and step_tab.is_contiguous() and step_tab.shape[1] == 4
+    assert mult_tab.dtype == torch.float32 and mult_tab.is_contiguous() and mult_tab.shape == step_tab.shape
+    ld = eps_cl.stride(1)
+    assert eps_cl.stride(0) == hw * ld
+    check(_lib.load().cd360_cfg_dpmpp2m_step_cl(_ptr(x), _ptr(old), _ptr(eps_cl), _ptr(step_tab), _ptr(mult_tab), _ptr(step), float(scale),
+                                               float("nan") if nb == 2 else float(scale_im), bs, hw, ld, _stream()), "cd360_cfg_dpmpp2m_step_cl")
+    return x
+
+
 def out_conv4_ok(H: int, W: int, cin: int) -> bool:
     return W in (32, 64, 128) and H % 2 == 0 and cin % 64 == 0 and H * W * cin * 2 < 2 ** 31
 

@@ -7,7 +7,7 @@ custom-diffusion360_amd/sgm/modules/diffusionmodules/), so the YAML sampler/deno
 
 Everything stays on the device and nothing synchronises: the sigma -> index quantisation is an argmin + gather on the GPU, and
 with `fused=True` the per-step tail (c_out scaling, 3-way or 2-way CFG combine, to_d, Euler update) is one HIP kernel
-(cd360_cfg_euler_step_f32) instead of ~10 tiny elementwise launches.
+(cd360_cfg_euler_step_f32) instead of ~10 tiny elementwise launches.  The second solver, DPMPP2MSampler (sampling.py:390-465), is at the end.
 """
 from __future__ import annotations
 
@@ -278,3 +278,126 @@ def fused_cfg3_euler_step(denoiser: "DiscreteDenoiser", network: Callable, x: to
                           scale: float, scale_im: float, fused: bool = True) -> torch.Tensor:
     """fused_cfg_euler_step under ScheduledCFGImgTextRef(scale, scale_im): the three-branch step by its earlier name."""
     return fused_cfg_euler_step(denoiser, network, x, sigma, sigma_next, ScheduledCFGImgTextRef(scale, scale_im), fused=fused)
+
+
+# ----------------------------------------------------------------------------------------------- DPM++ 2M
+def to_neg_log_sigma(sigma):  # sampling_utils.py
+    return sigma.log().neg()
+
+
+def to_sigma(neg_log_sigma):
+    return neg_log_sigma.neg().exp()
+
+
+class DPMPP2MSampler:
+    """DPM-Solver++(2M): x' = m1 x - m2 dd with dd = denoised on the first step and where sigma_next = 0, (1 + 1/2r) denoised - (1/2r) old_denoised
+    otherwise (sampling.py:390-465).  One network evaluation per step, deterministic.
+
+    The reference's class does not run in its own fork as written: BaseDiffusionSampler.denoise returns (denoised, rgb_list), sampler_step
+    multiplies that tuple, and __call__ returns x alone where DiffusionEngine.sample unpacks two values.  Here `denoise` is unpacked -- the
+    arithmetic is the reference's, operation by operation --, the rgb_list of the last denoise call is kept on the instance, and __call__
+    returns (x, rgb_list)."""
+
+    def __init__(self, discretization_config=None, num_steps: Optional[int] = None, guider_config=None, verbose: bool = False, device: str = "cuda"):
+        from sgm.util import instantiate_from_config
+        self.num_steps = num_steps
+        self.discretization = instantiate_from_config(discretization_config) if discretization_config else LegacyDDPMDiscretization()
+        self.guider = instantiate_from_config(guider_config) if guider_config else IdentityGuider()
+        self.verbose, self.device = verbose, device
+        self.rgb_list = None
+
+    prepare_sampling_loop = EulerEDMSampler.prepare_sampling_loop
+    denoise = EulerEDMSampler.denoise
+
+    def get_variables(self, sigma, next_sigma, previous_sigma=None):
+        t, t_next = [to_neg_log_sigma(s) for s in (sigma, next_sigma)]
+        h = t_next - t
+        if previous_sigma is not None:
+            h_last = t - to_neg_log_sigma(previous_sigma)
+            r = h_last / h
+            return h, r, t, t_next
+        return h, None, t, t_next
+
+    def get_mult(self, h, r, t, t_next, previous_sigma):
+        mult1 = to_sigma(t_next) / to_sigma(t)
+        mult2 = (-h).expm1()
+        if previous_sigma is not None:
+            mult3 = 1 + 1 / (2 * r)
+            mult4 = 1 / (2 * r)
+            return mult1, mult2, mult3, mult4
+        return mult1, mult2
+
+    def sampler_step(self, old_denoised, previous_sigma, sigma, next_sigma, denoiser, x, cond, uc=None):
+        denoised, self.rgb_list = self.denoise(x, denoiser, sigma, cond, uc)
+        h, r, t, t_next = self.get_variables(sigma, next_sigma, previous_sigma)
+        mult = [append_dims(m, x.ndim) for m in self.get_mult(h, r, t, t_next, previous_sigma)]
+        x_standard = mult[0] * x - mult[1] * denoised
+        if old_denoised is None or torch.sum(next_sigma) < 1e-14:  # first step, or all noise levels 0: the first-order update
+            return x_standard, denoised
+        denoised_d = mult[2] * denoised - mult[3] * old_denoised
+        x_advanced = mult[0] * x - mult[1] * denoised_d
+        return torch.where(append_dims(next_sigma, x.ndim) > 0.0, x_advanced, x_standard), denoised
+
+    def __call__(self, denoiser: Callable, x, cond: Dict, uc=None, num_steps=None, **kwargs):
+        x, s_in, sigmas, num_sigmas, cond, uc = self.prepare_sampling_loop(x, cond, uc, num_steps)
+        old_denoised = None
+        for i in range(num_sigmas - 1):
+            x, old_denoised = self.sampler_step(old_denoised, None if i == 0 else s_in * sigmas[i - 1], s_in * sigmas[i], s_in * sigmas[i + 1],
+                                                denoiser, x, cond, uc=uc)
+        return x, self.rgb_list
+
+    forward = __call__
+
+
+def dpmpp2m_multipliers(sigmas: torch.Tensor) -> torch.Tensor:
+    """The per-schedule table of DPMPP2MSampler: sigmas [n + 1] (the discretisation's output, last = 0) -> [n, 4] fp32 (m1, m2, m3, m4), row i
+    = get_variables / get_mult of step i in the reference's own operations and order.  Row 0 and every row with sigma_next < 1e-14 get
+    (m3, m4) = (1, 0): the reference's first-order shortcut (sampling.py:433-435), which the kernels read as "do not touch old"; the last
+    row of LegacyDDPMDiscretization comes out as (0, -1, 1, 0), i.e. x' = d0.
+    Computed in CPU fp32 whatever device `sigmas` lives on, and uploaded by the caller: graph, eager and fresh samplers share its bits."""
+    sig = sigmas.detach().to("cpu", torch.float32)
+    one = DPMPP2MSampler.__new__(DPMPP2MSampler)
+    rows = []
+    for i in range(sig.numel() - 1):
+        s, sn = sig[i].reshape(1), sig[i + 1].reshape(1)
+        prev = None if i == 0 or float(sn) < 1e-14 else sig[i - 1].reshape(1)
+        m = one.get_mult(*one.get_variables(s, sn, prev), prev)
+        rows.append(torch.cat(list(m) + ([torch.ones(1), torch.zeros(1)] if prev is None else [])))
+    return torch.stack(rows).contiguous()
+
+
+def cfg_dpmpp2m_update(x: torch.Tensor, eps: torch.Tensor, old: Optional[torch.Tensor], sigma: torch.Tensor, mult: torch.Tensor, scale: float,
+                       scale_im: Optional[float] = None, fused: bool = True):
+    """One fused tail of a CFG DPM++ 2M step with EpsScaling -> (x', d0): den_b = x - sigma eps_b, d0 = the guider's combine as in
+    cfg_euler_update, dd = d0 if m4 == 0 else m3 d0 - m4 old, x' = m1 x - m2 dd; mult = one row of dpmpp2m_multipliers, `old` = the d0 the
+    previous step returned (not read when m4 == 0: None is fine there).  fused=False: the same chain in plain torch, in the kernels' order."""
+    nb = 2 if scale_im is None else 3
+    if eps.shape[0] != nb * x.shape[0]:
+        raise ValueError(f"eps holds {eps.shape[0]} rows; the {nb}-branch step on {x.shape[0]} latents needs {nb * x.shape[0]}")
+    if fused and x.is_cuda:
+        from . import ops
+        return ops.cfg_dpmpp2m_step(x, eps, torch.empty_like(x) if old is None else old, sigma, mult, scale, scale_im)
+    if nb == 2:
+        e_u, e_c = eps.float().chunk(2)
+        du, dc = x - sigma * e_u, x - sigma * e_c
+        d0 = du + scale * (dc - du)
+    else:
+        e_u, e_ic, e_c = eps.float().chunk(3)
+        du, dic, dc = x - sigma * e_u, x - sigma * e_ic, x - sigma * e_c
+        d0 = du + scale * (dc - dic) + scale_im * (dic - du)
+    m1, m2, m3, m4 = mult.reshape(4).unbind()
+    dd = d0 if float(m4) == 0.0 else m3 * d0 - m4 * old
+    return m1 * x - m2 * dd, d0
+
+
+def fused_cfg_dpmpp2m_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, old: Optional[torch.Tensor], sigma: torch.Tensor,
+                           mult: torch.Tensor, guider, fused: bool = True):
+    """ONE step of DPMPP2MSampler.sampler_step (sampling.py:413-445) in the form the sampling job launches it: fused_cfg_euler_step with the
+    tail replaced -- x' , d0 = cfg_dpmpp2m_update(x, eps, old, sigma, mult): cd360_cfg_dpmpp2m_step_f32.  `mult` = row i of
+    dpmpp2m_multipliers(sigmas) for sigma = sigmas[i]; `old` = the d0 step i - 1 returned.  Returns (x', d0)."""
+    scale, scale_im = guider_scales(guider)
+    nb = guider.branches
+    xb = x.expand(nb, *x.shape[1:]) if x.shape[0] == 1 else torch.cat([x] * nb)
+    x_in, c_noise, _, _, _ = denoiser.network_inputs(xb, sigma.expand(xb.shape[0]), {})
+    eps = network(x_in, c_noise)
+    return cfg_dpmpp2m_update(x, eps.contiguous(), old, sigma.reshape(1), mult, scale, scale_im, fused=fused)

@@ -125,6 +125,89 @@ __global__ __launch_bounds__(256) void cfg_euler_step_cl_kernel(float* __restric
   }
 }
 
+// ---- DPM++ 2M (sampling.py:390-465, DPMPP2MSampler.sampler_step) on the same CFG combine: the second-order multistep update in table form.
+// Per element, with s = sigma of the step and (m1, m2, m3, m4) one row of a per-schedule multiplier table (cd360/sampler.py::dpmpp2m_multipliers:
+// get_variables / get_mult evaluated once per schedule on the host, (m3, m4) = (1, 0) for the first step and for sigma_next = 0):
+//   den_b = x - s eps_b;  d0 = the CFG combine of cfg_euler_step_cl_kernel, same order
+//   dd    = (m4 == 0) ? d0 : m3 d0 - m4 old          `old` (the previous step's d0) is NOT read when m4 == 0: on the first step of an image it holds
+//                                                    the previous image's value or uninitialised memory, and 0 * NaN must not reach x
+//   x'    = m1 x - m2 dd;  old' = d0
+// -ffp-contract=off: one fp32 rounding per operation, in this order (tests/test_dpmpp2m_gpu.py holds both kernels to it bit for bit).
+template <int NB>
+__device__ __forceinline__ float cfg_combine(float xv, float s, float e_u, float e_i, float e_c, float scale, float scale_im) {
+  static_assert(NB == 2 || NB == 3, "two or three CFG branches");
+  if constexpr (NB == 3) {
+    const float du = xv - s * e_u, dic = xv - s * e_i, dc = xv - s * e_c;
+    return du + scale * (dc - dic) + scale_im * (dic - du);
+  } else {
+    const float du = xv - s * e_u, dc = xv - s * e_c;
+    return du + scale * (dc - du);
+  }
+}
+
+__device__ __forceinline__ float dpmpp2m_update(float xv, float d0, float ov, float m1, float m2, float m3, float m4, bool multi) {
+  const float dd = multi ? m3 * d0 - m4 * ov : d0;
+  return m1 * xv - m2 * dd;
+}
+
+// x, old [bs, 4, HW] fp32, both updated IN PLACE; eps as for cfg_euler_step_cl_kernel; tab [nsteps, 4] (column 0 = sigma), mult [nsteps, 4]
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_dpmpp2m_step_cl_kernel(float* __restrict__ x, float* __restrict__ old, const uint16_t* __restrict__ eps,
+                                                                  const float* __restrict__ tab, const float* __restrict__ mult,
+                                                                  const int* __restrict__ step, float scale, float scale_im, int bs, long HW, int ld) {
+  const int idx = *step;
+  const float s = tab[idx * 4];
+  const float m1 = mult[idx * 4], m2 = mult[idx * 4 + 1], m3 = mult[idx * 4 + 2], m4 = mult[idx * 4 + 3];
+  const bool multi = m4 != 0.f;  // one table scalar: uniform over the launch
+  const long total = (long)bs * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long smp = i / HW, px = i - smp * HW;
+    const u32x2 eu = *reinterpret_cast<const u32x2*>(eps + ((0 * bs + smp) * HW + px) * ld);
+    u32x2 ei = eu;  // (NB = 2: unused)
+    if constexpr (NB == 3) ei = *reinterpret_cast<const u32x2*>(eps + ((1 * bs + smp) * HW + px) * ld);
+    const u32x2 ec = *reinterpret_cast<const u32x2*>(eps + (((NB - 1) * bs + smp) * HW + px) * ld);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float e_u = (c & 1) ? bf16hi_to_f32(eu[c >> 1]) : bf16lo_to_f32(eu[c >> 1]);
+      const float e_i = (c & 1) ? bf16hi_to_f32(ei[c >> 1]) : bf16lo_to_f32(ei[c >> 1]);
+      const float e_c = (c & 1) ? bf16hi_to_f32(ec[c >> 1]) : bf16lo_to_f32(ec[c >> 1]);
+      const long at = (smp * 4 + c) * HW + px;
+      const float xv = x[at];
+      const float ov = multi ? old[at] : 0.f;
+      const float d0 = cfg_combine<NB>(xv, s, e_u, e_i, e_c, scale, scale_im);
+      x[at] = dpmpp2m_update(xv, d0, ov, m1, m2, m3, m4, multi);
+      old[at] = d0;
+    }
+  }
+}
+
+// the un-staged form: x, old [n] fp32, eps [NB n] fp32 (branch b at eps + b n), sigma [1], mult [4] device tensors -> out, old_out [n]
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_dpmpp2m_step_kernel(const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ old,
+                                                               const float* __restrict__ sigma, const float* __restrict__ mult, float scale,
+                                                               float scale_im, float* __restrict__ out, float* __restrict__ old_out, long n) {
+  const float s = *sigma;
+  const float m1 = mult[0], m2 = mult[1], m3 = mult[2], m4 = mult[3];
+  const bool multi = m4 != 0.f;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float xv = x[i];
+    const float ov = multi ? old[i] : 0.f;
+    const float d0 = cfg_combine<NB>(xv, s, eps[i], NB == 3 ? eps[n + i] : 0.f, eps[(NB - 1) * n + i], scale, scale_im);
+    out[i] = dpmpp2m_update(xv, d0, ov, m1, m2, m3, m4, multi);
+    old_out[i] = d0;
+  }
+}
+
+inline unsigned tail_grid(long total) {  // grid-stride kernels: one thread per element up to 65536 workgroups
+  const long blocks = (total + 255) / 256;
+  return (unsigned)(blocks > 65536 ? 65536 : blocks);
+}
+
+inline bool overlap(const void* a, const void* b, long bytes) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return pa < pb + (uintptr_t)bytes && pb < pa + (uintptr_t)bytes;
+}
+
 }  // namespace
 
 // See the kernel for layouts.  Cout % 8 == 0, E % 8 == 0; w_k36 = the input convolution's weight as [36, Cout] fp32 (k = (ky * 3 + kx) * 4 + ci).
@@ -158,6 +241,43 @@ extern "C" int cd360_cfg_euler_step_cl(void* x, const void* eps, const void* ste
   else
     hipLaunchKernelGGL(cfg_euler_step_cl_kernel<3>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (float*)x,
                        (const uint16_t*)eps, (const float*)step_tab, (const int*)step, scale, scale_im, bs, (long)HW, ld);
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// include/cd360_solvers.h.  x, old [bs, 4, HW] fp32 IN PLACE (distinct buffers); eps, ld and the NaN scale_im as for cd360_cfg_euler_step_cl;
+// step_tab [nsteps, 4] (sigma = column 0), mult_tab [nsteps, 4] = (m1, m2, m3, m4)
+extern "C" int cd360_cfg_dpmpp2m_step_cl(void* x, void* old, const void* eps, const void* step_tab, const void* mult_tab, const void* step, float scale,
+                                         float scale_im, int bs, int64_t HW, int ld, void* stream) {
+  if (!x || !old || !eps || !step_tab || !mult_tab || !step || bs <= 0 || HW <= 0 || ld < 4 || ld % 4) return CD360_ERR_ARG;
+  if ((uintptr_t)eps % 8 || ((uintptr_t)x | (uintptr_t)old) % 4) return CD360_ERR_ARG;
+  const long total = (long)bs * HW;
+  if (overlap(x, old, total * 4 * (long)sizeof(float))) return CD360_ERR_ARG;
+  if (std::isnan(scale_im))
+    hipLaunchKernelGGL(cfg_dpmpp2m_step_cl_kernel<2>, dim3(tail_grid(total)), dim3(256), 0, (hipStream_t)stream, (float*)x, (float*)old,
+                       (const uint16_t*)eps, (const float*)step_tab, (const float*)mult_tab, (const int*)step, scale, 0.f, bs, (long)HW, ld);
+  else
+    hipLaunchKernelGGL(cfg_dpmpp2m_step_cl_kernel<3>, dim3(tail_grid(total)), dim3(256), 0, (hipStream_t)stream, (float*)x, (float*)old,
+                       (const uint16_t*)eps, (const float*)step_tab, (const float*)mult_tab, (const int*)step, scale, scale_im, bs, (long)HW, ld);
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// x, old [n] fp32, eps [3n] fp32 (u | ic | c) or, for a NaN scale_im, [2n] (u | c); sigma [1], mult [4] device tensors; out, old_out [n]: buffers of
+// their own (neither an input, nor each other)
+extern "C" int cd360_cfg_dpmpp2m_step_f32(const void* x, const void* eps, const void* old, const void* sigma, const void* mult, float scale,
+                                          float scale_im, void* out, void* old_out, int64_t n, void* stream) {
+  if (!x || !eps || !old || !sigma || !mult || !out || !old_out || n <= 0) return CD360_ERR_ARG;
+  const long bytes = (long)n * (long)sizeof(float);
+  if (overlap(x, old, bytes) || overlap(out, old_out, bytes) || overlap(out, x, bytes) || overlap(out, old, bytes) || overlap(old_out, x, bytes) ||
+      overlap(old_out, old, bytes))
+    return CD360_ERR_ARG;
+  if (std::isnan(scale_im))
+    hipLaunchKernelGGL(cfg_dpmpp2m_step_kernel<2>, dim3(tail_grid(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)eps,
+                       (const float*)old, (const float*)sigma, (const float*)mult, scale, 0.f, (float*)out, (float*)old_out, (long)n);
+  else
+    hipLaunchKernelGGL(cfg_dpmpp2m_step_kernel<3>, dim3(tail_grid(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)eps,
+                       (const float*)old, (const float*)sigma, (const float*)mult, scale, scale_im, (float*)out, (float*)old_out, (long)n);
   CD360_LAUNCH_CHECK();
   return CD360_OK;
 }
