@@ -26,15 +26,22 @@ class Sampler:
     replayed: ~3000 launches per step are then issued by the GPU front end instead of the Python interpreter.
     `solver`: "euler" (EulerEDMSampler, sampling.py:85-136) or "dpmpp2m" (DPMPP2MSampler, sampling.py:390-465: second order, multistep,
     the same one UNet evaluation per step); the step's tail kernel is the only difference.  DPM++ 2M carries the previous step's denoised
-    latent in `self.gd`, so `step(x, i)` for i > 0 must follow `step(., i - 1)` of the SAME image (`eps()` is unaffected)."""
+    latent in `self.gd`, so `step(x, i)` for i > 0 must follow `step(., i - 1)` of the SAME image (`eps()` is unaffected).
+    "euler_a" (EulerAncestralSampler, sampling.py:236-273, 340-347: stochastic, `eta` / `s_noise` as the reference's constructor takes them)
+    draws its noise INSIDE the tail kernel as a pure function of (`seed`, the row's noise stream, step index, channel, pixel)
+    (include/cd360_stochastic.h), so graph, eager, fresh and un-staged runs add the same bits and no state is kept between steps.
+    `noise_streams`: one id per replay row (default: stream 0 everywhere -- all poses of a job share the injected noise, as
+    sample.py:290-292 shares the start noise); `reseed` / `set_noise_streams` rewrite the device buffers, no re-capture."""
 
-    SOLVERS = ("euler", "dpmpp2m")
+    SOLVERS = ("euler", "dpmpp2m", "euler_a")
 
-    def __init__(self, net, pose, ctx, y, n_steps, scale=7.5, scale_im=3.5, use_graph=False, prefetch=None, graph_render=True, solver="euler"):
+    def __init__(self, net, pose, ctx, y, n_steps, scale=7.5, scale_im=3.5, use_graph=False, prefetch=None, graph_render=True, solver="euler",
+                 eta=1.0, s_noise=1.0, seed=0, noise_streams=None):
         from cd360 import sampler as S
         if solver not in self.SOLVERS:
-            raise ValueError(f"solver {solver!r}: the job sampler serves {' and '.join(self.SOLVERS)}")
+            raise ValueError(f"solver {solver!r}: the job sampler serves {', '.join(self.SOLVERS)}")
         self.solver = solver
+        self.eta, self.s_noise, self.seed, self.noise_streams = eta, s_noise, seed, noise_streams
         self.net, self.pose, self.n_steps = net, pose, n_steps
         if use_graph:  # the graphs read the cameras through ONE buffer this sampler owns (retarget rewrites it in place)
             from sgm.modules.utils_cameraray import PoseBuffer
@@ -129,10 +136,12 @@ class Sampler:
         nbs, (H, W) = self.y.shape[0], x.shape[2:]  # B bs images
         self.h0 = torch.empty(nbs, H * W, conv.out_channels, dtype=dt, device=dev)
         self.emb_act = torch.empty_like(self.lab)
-        if self.solver == "dpmpp2m":
+        if self.solver != "euler":
             self._build_solver(x)
 
     def _build_solver(self, x):
+        if self.solver == "euler_a":
+            return self._build_ancestral(x)
         """DPM++ 2M state: the multiplier table (host fp32, uploaded: the same bits in every sampler of a schedule), the un-staged step's
         4-float row buffer, and gd = the previous step's denoised latent d0, shaped like gx and shared by both captured graphs.  retarget()
         does not reset gd: row 0 of the table has m4 = 0 and the kernels then never read it -- which is also why step(x, i) for i > 0 must
@@ -141,6 +150,43 @@ class Sampler:
         self.mult_tab = dpmpp2m_multipliers(self.sigmas).to(x.device)
         self.gm = self.mult_tab[0].clone()
         self.gd = torch.zeros_like(x)
+
+    def _build_ancestral(self, x):
+        """Ancestral Euler state: the (sigma_down, sigma_up, s_noise, 0) table (host fp32, uploaded: the same bits in every sampler of a
+        schedule), the un-staged step's 4-float row buffer and its step index, and the generator's seed / stream-id buffers the tail kernels
+        read on the device.  Nothing is carried from one step to the next."""
+        from cd360.sampler import DeviceNoise, euler_ancestral_table, seed_words
+        dev = x.device
+        self.anc_tab = euler_ancestral_table(self.sigmas, self.eta, self.s_noise).to(dev)
+        self.ga = self.anc_tab[0].clone()
+        self.seed_buf = torch.tensor([seed_words(self.seed)], dtype=torch.int64, device=dev)
+        self.streams_buf = torch.zeros(x.shape[0], dtype=torch.int32, device=dev)
+        if self.noise_streams is not None:
+            self.set_noise_streams(self.noise_streams)
+        if getattr(self, "gi", None) is None:  # (the staged step owns gi; the un-staged one gets its own step index)
+            self._iota = torch.arange(self.n_steps, dtype=torch.int32, device=dev)
+            self.gi = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.noise = DeviceNoise(self.seed_buf, self.streams_buf, self.gi)
+
+    def reseed(self, seed):
+        """Another seed for the injected noise: one 8-byte copy into the buffer the captured tails read (no re-capture)."""
+        from cd360.sampler import seed_words
+        if self.solver != "euler_a":
+            raise ValueError(f"solver {self.solver!r} draws no noise")
+        self.seed = seed
+        if getattr(self, "seed_buf", None) is not None:
+            self.seed_buf.copy_(torch.tensor([seed_words(seed)], dtype=torch.int64))
+
+    def set_noise_streams(self, ids):
+        """One noise stream id per replay row (rows of equal id receive equal noise): copied into the buffer the captured tails read."""
+        if self.solver != "euler_a":
+            raise ValueError(f"solver {self.solver!r} draws no noise")
+        ids = [int(v) for v in ids]
+        if len(ids) != self.bs:
+            raise ValueError(f"{len(ids)} noise stream ids for {self.bs} replay rows")
+        self.noise_streams = ids
+        if getattr(self, "streams_buf", None) is not None:
+            self.streams_buf.copy_(torch.tensor(ids, dtype=torch.int32))
 
     def _math_staged(self):
         """One sampler step on the static buffers, in place on self.gx: stage-in kernel (rep = B) -> UNet trunk -> fused [c_out, CFG, to_d,
@@ -151,18 +197,23 @@ class Sampler:
         eps_cl = self.net.forward_staged(self.h0, self.emb_act, self.ctx, self.pose, H, W)
         if self.solver == "dpmpp2m":  # x and gd in place: [c_out, CFG, multistep update]
             return ops.cfg_dpmpp2m_step_cl(self.gx, self.gd, eps_cl, self.step_tab, self.mult_tab, self.gi, self.scale, self.scale_im)
+        if self.solver == "euler_a":  # [c_out, CFG, to_d, Euler to sigma_down, + noise sigma_up]
+            return ops.cfg_euler_ancestral_step_cl(self.gx, eps_cl, self.step_tab, self.anc_tab, self.gi, self.seed_buf, self.streams_buf,
+                                                   self.scale, self.scale_im)
         return ops.cfg_euler_step_cl(self.gx, eps_cl, self.step_tab, self.gi, self.scale, self.scale_im)
 
     def _math(self, x, s, s_next, t_unused=None):
         """One sampler step = guider.prepare_inputs -> DiscreteDenoiser (sigma -> table index, c_in) -> UNet -> fused
         [c_out, CFG, to_d, Euler] kernel -- or, for DPM++ 2M, the [c_out, CFG, multistep update] kernel on the row in self.gm, which also
-        moves this step's d0 into self.gd."""
-        from cd360.sampler import fused_cfg_dpmpp2m_step, fused_cfg_euler_step
+        moves this step's d0 into self.gd; for ancestral Euler the kernel on the row in self.ga and the step index in self.gi."""
+        from cd360.sampler import fused_cfg_dpmpp2m_step, fused_cfg_euler_ancestral_step, fused_cfg_euler_step
         unet = lambda x_in, c_noise: self.net(x_in, timesteps=c_noise, context=self.ctx, y=self.y, pose=self.pose)[0]  # noqa: E731
         if self.solver == "dpmpp2m":
             out, d0 = fused_cfg_dpmpp2m_step(self.denoiser, unet, x, self.gd, s, self.gm, self.guider)
             self.gd.copy_(d0)
             return out
+        if self.solver == "euler_a":
+            return fused_cfg_euler_ancestral_step(self.denoiser, unet, x, s, self.ga, self.guider, noise=self.noise)
         return fused_cfg_euler_step(self.denoiser, unet, x, s, s_next, self.guider)
 
     @torch.no_grad()
@@ -241,7 +292,7 @@ class Sampler:
         self.gx, self.gs, self.gt = x.clone(), torch.stack([s, s_next]), t.clone()
         if self.staged:
             self._build_stage(x)
-        elif self.solver == "dpmpp2m":
+        elif self.solver != "euler":
             self._build_solver(x)
         self._render()
         if self.staged:
@@ -309,11 +360,19 @@ class Sampler:
                 if getattr(self, "mult_tab", None) is None:
                     self._build_solver(x)
                 self.gm.copy_(self.mult_tab[i])
+            if self.solver == "euler_a":
+                if getattr(self, "anc_tab", None) is None:
+                    self._build_solver(x)
+                self.ga.copy_(self.anc_tab[i])
+                self.gi.copy_(self._iota[i:i + 1])
             return self._math(x, s, s_next, t)
         self.prepare(x)
         self.gx.copy_(x)
         if self.solver == "dpmpp2m":
             self.gm.copy_(self.mult_tab[i])
+        if self.solver == "euler_a":
+            self.ga.copy_(self.anc_tab[i])
+            self.gi.copy_(self._iota[i:i + 1])
         self.gs[0].copy_(s)
         self.gs[1].copy_(s_next)
         self.gt.copy_(t)

@@ -1313,6 +1313,67 @@ def cfg_dpmpp2m_step_cl(x: torch.Tensor, old: torch.Tensor, eps_cl: torch.Tensor
     return x
 
 
+def _noise_args(seed: torch.Tensor, streams: Optional[torch.Tensor], step: torch.Tensor, bs: int):
+    assert seed.dtype == torch.int64 and seed.numel() == 1 and step.dtype == torch.int32 and step.numel() == 1
+    assert streams is None or (streams.dtype == torch.int32 and streams.numel() == bs and streams.is_contiguous())
+
+
+def sampler_noise(seed: torch.Tensor, streams: Optional[torch.Tensor], step: torch.Tensor, bs: int, H: int, W: int) -> torch.Tensor:
+    """Standard normals [bs, 4, H, W] fp32 as a pure function of (seed, streams[row], step, channel, pixel): Philox4x32-10 + Box-Muller
+    (cd360_sampler_noise_f32, include/cd360_stochastic.h).  seed: device int64[1], step: device int32[1], streams: device int32[bs] or None
+    (stream 0 for every row).  Rows of equal stream id hold equal bits whatever bs is."""
+    _need_gpu(seed, streams, step)
+    _noise_args(seed, streams, step, bs)
+    out = torch.empty((bs, 4, H, W), dtype=torch.float32, device=seed.device)
+    check(_lib.load().cd360_sampler_noise_f32(_ptr(out), _ptr(seed), _ptr(streams), _ptr(step), bs, H * W, _stream()), "cd360_sampler_noise_f32")
+    return out
+
+
+def cfg_euler_ancestral_step(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, anc: torch.Tensor, seed: torch.Tensor,
+                             streams: Optional[torch.Tensor], step: torch.Tensor, scale: float, scale_im: Optional[float]):
+    """One ancestral Euler tail (cd360_cfg_euler_ancestral_step_f32, include/cd360_stochastic.h): x [bs, 4, H, W] fp32, eps [3 bs, 4, H, W]
+    fp32 (u | ic | c) or, with scale_im=None, [2 bs, ...] (u | c), sigma a 1-element and anc = (sigma_down, sigma_up, s_noise, 0) a
+    4-element fp32 device tensor; the noise is sampler_noise(seed, streams, step, ...), drawn inside the kernel (none when sigma_up == 0)
+    -> x', a new tensor."""
+    _need_gpu(x, eps, sigma, anc, seed, streams, step)
+    nb = _cfg_branches(scale_im)
+    if eps.shape[0] != nb * x.shape[0] or eps.numel() != nb * x.numel():
+        raise ValueError(f"eps holds {eps.shape[0]} rows of {tuple(eps.shape[1:])}; the {nb}-branch step on x {tuple(x.shape)} needs {nb * x.shape[0]}")
+    assert x.dtype == torch.float32 and eps.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous() and x.ndim == 4 and x.shape[1] == 4
+    assert sigma.dtype == torch.float32 and sigma.numel() == 1 and anc.dtype == torch.float32 and anc.numel() == 4 and anc.is_contiguous()
+    bs = x.shape[0]
+    _noise_args(seed, streams, step, bs)
+    out = torch.empty_like(x)
+    check(_lib.load().cd360_cfg_euler_ancestral_step_f32(_ptr(x), _ptr(eps), _ptr(sigma), _ptr(anc), _ptr(seed), _ptr(streams), _ptr(step),
+                                                        float(scale), float("nan") if nb == 2 else float(scale_im), _ptr(out), bs,
+                                                        x.shape[2] * x.shape[3], _stream()), "cd360_cfg_euler_ancestral_step_f32")
+    return out
+
+
+def cfg_euler_ancestral_step_cl(x: torch.Tensor, eps_cl: torch.Tensor, step_tab: torch.Tensor, anc_tab: torch.Tensor, step: torch.Tensor,
+                                seed: torch.Tensor, streams: Optional[torch.Tensor], scale: float, scale_im: Optional[float]):
+    """Ancestral Euler tail of a captured sampling step, IN PLACE on x [bs, 4, H, W] fp32 (cd360_cfg_euler_ancestral_step_cl): eps_cl as
+    for cfg_euler_step_cl, sigma = step_tab[step][0], (sigma_down, sigma_up, s_noise, 0) = anc_tab[step], the noise =
+    sampler_noise(seed, streams, step, ...) drawn inside the kernel (none when sigma_up == 0)."""
+    _need_gpu(x, eps_cl, step_tab, anc_tab, step, seed, streams)
+    nb = _cfg_branches(scale_im)
+    bs = x.shape[0]
+    hw = x.shape[2] * x.shape[3]
+    if eps_cl.shape[0] != nb * bs:
+        raise ValueError(f"eps_cl holds {eps_cl.shape[0]} images; the {nb}-branch step on {bs} latents needs {nb * bs}")
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == 4 and eps_cl.dtype == torch.bfloat16
+    assert eps_cl.shape[1] == hw and eps_cl.shape[2] >= 4 and eps_cl.stride(2) == 1
+    assert step_tab.dtype == torch.float32 and step_tab.is_contiguous() and step_tab.shape[1] == 4
+    assert anc_tab.dtype == torch.float32 and anc_tab.is_contiguous() and anc_tab.shape == step_tab.shape
+    _noise_args(seed, streams, step, bs)
+    ld = eps_cl.stride(1)
+    assert eps_cl.stride(0) == hw * ld
+    check(_lib.load().cd360_cfg_euler_ancestral_step_cl(_ptr(x), _ptr(eps_cl), _ptr(step_tab), _ptr(anc_tab), _ptr(step), _ptr(seed),
+                                                       _ptr(streams), float(scale), float("nan") if nb == 2 else float(scale_im), bs, hw, ld,
+                                                       _stream()), "cd360_cfg_euler_ancestral_step_cl")
+    return x
+
+
 def out_conv4_ok(H: int, W: int, cin: int) -> bool:
     return W in (32, 64, 128) and H % 2 == 0 and cin % 64 == 0 and H * W * cin * 2 < 2 ** 31
 

@@ -7,7 +7,7 @@ custom-diffusion360_amd/sgm/modules/diffusionmodules/), so the YAML sampler/deno
 
 Everything stays on the device and nothing synchronises: the sigma -> index quantisation is an argmin + gather on the GPU, and
 with `fused=True` the per-step tail (c_out scaling, 3-way or 2-way CFG combine, to_d, Euler update) is one HIP kernel
-(cd360_cfg_euler_step_f32) instead of ~10 tiny elementwise launches.  The second solver, DPMPP2MSampler (sampling.py:390-465), is at the end.
+(cd360_cfg_euler_step_f32) instead of ~10 tiny elementwise launches.  DPMPP2MSampler and EulerAncestralSampler are at the end.
 """
 from __future__ import annotations
 
@@ -401,3 +401,162 @@ def fused_cfg_dpmpp2m_step(denoiser: "DiscreteDenoiser", network: Callable, x: t
     x_in, c_noise, _, _, _ = denoiser.network_inputs(xb, sigma.expand(xb.shape[0]), {})
     eps = network(x_in, c_noise)
     return cfg_dpmpp2m_update(x, eps.contiguous(), old, sigma.reshape(1), mult, scale, scale_im, fused=fused)
+
+
+# ----------------------------------------------------------------------------------------------- ancestral Euler
+def get_ancestral_step(sigma_from, sigma_to, eta=1.0):
+    """(sigma_down, sigma_up) of one ancestral step, the reference's expression in the reference's operation order (sampling_utils.py:27-36).
+    eta = 0: (sigma_to, 0) with a zero TENSOR where the reference hands back the Python float 0.0 that its own append_dims then rejects."""
+    if not eta:
+        return sigma_to, torch.zeros_like(sigma_to)
+    sigma_up = torch.minimum(sigma_to, eta * (sigma_to ** 2 * (sigma_from ** 2 - sigma_to ** 2) / sigma_from ** 2) ** 0.5)
+    sigma_down = (sigma_to ** 2 - sigma_up ** 2) ** 0.5
+    return sigma_down, sigma_up
+
+
+def seed_words(seed: int) -> int:
+    """Any Python int -> the int64 whose 64 bits are the seed's low 64 bits (the device buffer's dtype; the Philox key is its two halves)."""
+    s = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return s - (1 << 64) if s >= (1 << 63) else s
+
+
+class DeviceNoise:
+    """The three device buffers that name one draw of the library's generator (include/cd360_stochastic.h): seed int64[1], streams
+    int32[bs] or None (stream 0 for every row), step int32[1].  A captured step reads all three on the device."""
+
+    def __init__(self, seed: torch.Tensor, streams: Optional[torch.Tensor], step: torch.Tensor):
+        self.seed, self.streams, self.step = seed, streams, step
+
+    def draw(self, x: torch.Tensor) -> torch.Tensor:
+        from . import ops
+        return ops.sampler_noise(self.seed, self.streams, self.step, x.shape[0], x.shape[2], x.shape[3])
+
+
+class EulerAncestralSampler:
+    """Ancestral Euler: x_e = x + (x - denoised) / sigma (sigma_down - sigma), then x' = x_e + noise s_noise sigma_up where sigma_next > 0
+    (sampling.py:236-273, 340-347).  One network evaluation per step, like EulerEDMSampler; stochastic.
+
+    The reference's class does not run in its own fork as written: BaseDiffusionSampler.denoise returns (denoised, rgb_list) and sampler_step
+    uses that tuple as a tensor, __call__ returns x alone where DiffusionEngine.sample unpacks two values, and eta = 0 hands the Python
+    float 0.0 to append_dims.  Here `denoise` is unpacked -- the arithmetic is the reference's, operation by operation --, the rgb_list of
+    the last denoise call is kept on the instance, __call__ returns (x, rgb_list), and eta = 0 is served as plain Euler (no noise drawn).
+
+    `noise_sampler` as in the reference: with seed=None it is torch.randn_like.  With seed=<int> it is the library's counter-based generator
+    (cd360_sampler_noise_f32: Philox4x32-10 + Box-Muller, stream 0, step = the number of draws since __call__ began), which is what
+    cd360.job.Sampler(solver="euler_a", seed=...) draws inside its captured step: GPU tensors only."""
+
+    def __init__(self, eta=1.0, s_noise=1.0, discretization_config=None, num_steps: Optional[int] = None, guider_config=None,
+                 verbose: bool = False, device: str = "cuda", seed: Optional[int] = None):
+        from sgm.util import instantiate_from_config
+        self.eta, self.s_noise = eta, s_noise
+        self.num_steps = num_steps
+        self.discretization = instantiate_from_config(discretization_config) if discretization_config else LegacyDDPMDiscretization()
+        self.guider = instantiate_from_config(guider_config) if guider_config else IdentityGuider()
+        self.verbose, self.device = verbose, device
+        self.rgb_list = None
+        self.seed, self._draws, self._noise = seed, 0, None
+        self.noise_sampler = (lambda x: torch.randn_like(x)) if seed is None else self._seeded_noise
+
+    prepare_sampling_loop = EulerEDMSampler.prepare_sampling_loop
+    denoise = EulerEDMSampler.denoise
+
+    def _seeded_noise(self, x):
+        if not x.is_cuda:
+            from ._lib import Cd360Error
+            raise Cd360Error("the seeded noise of EulerAncestralSampler is drawn by a HIP kernel; got a CPU tensor (seed=None draws torch.randn_like)")
+        if self._noise is None or self._noise.seed.device != x.device:
+            self._noise = DeviceNoise(torch.tensor([seed_words(self.seed)], dtype=torch.int64, device=x.device), None,
+                                      torch.zeros(1, dtype=torch.int32, device=x.device))
+        self._noise.step.fill_(self._draws)
+        self._draws += 1
+        return self._noise.draw(x)
+
+    def euler_step(self, x, d, dt):
+        return x + dt * d
+
+    def ancestral_euler_step(self, x, denoised, sigma, sigma_down):
+        d = (x - denoised) / append_dims(sigma, x.ndim)
+        dt = append_dims(sigma_down - sigma, x.ndim)
+        return self.euler_step(x, d, dt)
+
+    def ancestral_step(self, x, sigma, next_sigma, sigma_up):
+        if not self.eta:  # plain Euler: nothing drawn
+            return x
+        return torch.where(append_dims(next_sigma, x.ndim) > 0.0, x + self.noise_sampler(x) * self.s_noise * append_dims(sigma_up, x.ndim), x)
+
+    def sampler_step(self, sigma, next_sigma, denoiser, x, cond, uc=None):
+        sigma_down, sigma_up = get_ancestral_step(sigma, next_sigma, eta=self.eta)
+        denoised, self.rgb_list = self.denoise(x, denoiser, sigma, cond, uc)
+        x = self.ancestral_euler_step(x, denoised, sigma, sigma_down)
+        return self.ancestral_step(x, sigma, next_sigma, sigma_up)
+
+    def __call__(self, denoiser: Callable, x, cond: Dict, uc=None, num_steps=None, **kwargs):
+        x, s_in, sigmas, num_sigmas, cond, uc = self.prepare_sampling_loop(x, cond, uc, num_steps)
+        self._draws = 0
+        for i in range(num_sigmas - 1):
+            x = self.sampler_step(s_in * sigmas[i], s_in * sigmas[i + 1], denoiser, x, cond, uc)
+        return x, self.rgb_list
+
+    forward = __call__
+
+
+def euler_ancestral_table(sigmas: torch.Tensor, eta: float = 1.0, s_noise: float = 1.0) -> torch.Tensor:
+    """The per-schedule table of EulerAncestralSampler: sigmas [n + 1] (the discretisation's output, last = 0) -> [n, 4] fp32 rows
+    (sigma_down, sigma_up, s_noise, 0), row i = get_ancestral_step(sigmas[i], sigmas[i + 1], eta).  The last row comes out as (0, 0): no
+    noise where sigma_next = 0 (sampling.py:251-255); eta = 0 gives (sigma_next, 0) in every row: plain Euler.
+    Computed in CPU fp32 whatever device `sigmas` lives on, and uploaded by the caller: graph, eager and fresh samplers share its bits."""
+    sig = sigmas.detach().to("cpu", torch.float32)
+    down, up = get_ancestral_step(sig[:-1], sig[1:], eta=eta)
+    return torch.stack([down, up, torch.full_like(down, float(s_noise)), torch.zeros_like(down)], 1).contiguous()
+
+
+def cfg_euler_ancestral_update(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, anc_row: torch.Tensor, scale: float,
+                               scale_im: Optional[float] = None, noise=None, fused: bool = True) -> torch.Tensor:
+    """One fused tail of a CFG ancestral Euler step with EpsScaling: den_b = x - sigma eps_b, d0 = the guider's combine as in
+    cfg_euler_update, x_e = x + (x - d0) / sigma * (sigma_down - sigma), x' = x_e if sigma_up == 0 else x_e + (z * s_noise) * sigma_up, with
+    (sigma_down, sigma_up, s_noise, 0) = anc_row, one row of euler_ancestral_table.  `noise`: a DeviceNoise -- fused: ONE kernel that draws z
+    itself (cd360_cfg_euler_ancestral_step_f32) -- or a tensor z shaped like x (a caller's own draw): the kernel then computes x_e (its
+    sigma_up = 0 form) and the given z is added by torch in the kernel's order; not needed when sigma_up == 0.
+    fused=False: the same chain in plain torch, in the kernel's order."""
+    nb = 2 if scale_im is None else 3
+    if eps.shape[0] != nb * x.shape[0]:
+        raise ValueError(f"eps holds {eps.shape[0]} rows; the {nb}-branch step on {x.shape[0]} latents needs {nb * x.shape[0]}")
+    if fused and x.is_cuda and isinstance(noise, DeviceNoise):  # (nothing read back: this is the call a captured un-staged step makes)
+        from . import ops
+        return ops.cfg_euler_ancestral_step(x, eps, sigma, anc_row.reshape(4), noise.seed, noise.streams, noise.step, scale, scale_im)
+    sd, su, s_noise, _ = anc_row.reshape(4).unbind()
+    noisy = float(su) != 0.0
+    if noisy and noise is None:
+        raise ValueError("sigma_up != 0: the step needs `noise` (a DeviceNoise or a tensor shaped like x)")
+    if fused and x.is_cuda:
+        from . import ops
+        dry = DeviceNoise(torch.zeros(1, dtype=torch.int64, device=x.device), None, torch.zeros(1, dtype=torch.int32, device=x.device))
+        x_e = ops.cfg_euler_ancestral_step(x, eps, sigma, torch.stack([sd, torch.zeros_like(su), s_noise, torch.zeros_like(su)]),
+                                           dry.seed, None, dry.step, scale, scale_im)
+        return x_e + (noise * s_noise) * su if noisy else x_e
+    if nb == 2:
+        e_u, e_c = eps.float().chunk(2)
+        du, dc = x - sigma * e_u, x - sigma * e_c
+        d0 = du + scale * (dc - du)
+    else:
+        e_u, e_ic, e_c = eps.float().chunk(3)
+        du, dic, dc = x - sigma * e_u, x - sigma * e_ic, x - sigma * e_c
+        d0 = du + scale * (dc - dic) + scale_im * (dic - du)
+    x_e = x + (x - d0) / sigma * (sd - sigma)
+    if not noisy:
+        return x_e
+    z = noise.draw(x) if isinstance(noise, DeviceNoise) else noise
+    return x_e + (z * s_noise) * su
+
+
+def fused_cfg_euler_ancestral_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, sigma: torch.Tensor, anc_row: torch.Tensor,
+                                   guider, noise=None, fused: bool = True) -> torch.Tensor:
+    """ONE step of EulerAncestralSampler.sampler_step (sampling.py:340-347) in the form the sampling job launches it: fused_cfg_euler_step
+    with the tail replaced -- x' = cfg_euler_ancestral_update(x, eps, sigma, anc_row, noise=noise).  `anc_row` = row i of
+    euler_ancestral_table(sigmas, eta, s_noise) for sigma = sigmas[i]; `noise` as cfg_euler_ancestral_update takes it."""
+    scale, scale_im = guider_scales(guider)
+    nb = guider.branches
+    xb = x.expand(nb, *x.shape[1:]) if x.shape[0] == 1 else torch.cat([x] * nb)
+    x_in, c_noise, _, _, _ = denoiser.network_inputs(xb, sigma.expand(xb.shape[0]), {})
+    eps = network(x_in, c_noise)
+    return cfg_euler_ancestral_update(x, eps.contiguous(), sigma.reshape(1), anc_row, scale, scale_im, noise=noise, fused=fused)

@@ -198,6 +198,128 @@ __global__ __launch_bounds__(256) void cfg_dpmpp2m_step_kernel(const float* __re
   }
 }
 
+// ---- device noise + ancestral Euler (sampling.py:236-273, 340-347: AncestralSampler / EulerAncestralSampler.sampler_step) --------------------
+// Standard normals as a PURE FUNCTION of (seed, noise stream, step index, channel, pixel): Philox4x32-10 as published in Random123 (key = the
+// two halves of the seed, counter = (pixel, step, stream id, 0): the last word is a reserved domain tag), then Box-Muller on the four output
+// words.  One Philox call serves the four latent channels of a pixel.  Nothing here depends on the grid, on bs or on where a row sits in the
+// batch, so a graph replay, an eager launch, a fresh sampler and the un-staged route draw the same bits (include/cd360_stochastic.h).
+// Precise logf / sinf / cosf / sqrtf: the float64 restatement in tests/philox_ref.py is the yardstick.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t r[4]) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  r[0] = c0, r[1] = c1, r[2] = c2, r[3] = c3;
+}
+
+__device__ __forceinline__ void box_muller(uint32_t ra, uint32_t rb, float& za, float& zb) {
+  const float u1 = (float)((ra >> 8) + 1u) * 0x1p-24f;  // (0, 1]: exact in fp32
+  const float u2 = (float)(rb >> 8) * 0x1p-24f;         // [0, 1)
+  const float rad = sqrtf(-2.f * logf(u1));
+  const float ang = 6.2831855f * u2;
+  za = rad * cosf(ang);
+  zb = rad * sinf(ang);
+}
+
+// z[c] = the noise of channel c of pixel px in noise stream `strm` at step `step`
+__device__ __forceinline__ void sampler_noise4(uint32_t px, uint32_t step, uint32_t strm, uint32_t k0, uint32_t k1, float z[4]) {
+  uint32_t r[4];
+  philox4x32_10(px, step, strm, 0u, k0, k1, r);
+  box_muller(r[0], r[1], z[0], z[1]);
+  box_muller(r[2], r[3], z[2], z[3]);
+}
+
+// out [bs, 4, HW] fp32; seed: device int64 read as (low, high) 32-bit words; streams [bs] int32 or null (stream 0 for every row)
+__global__ __launch_bounds__(256) void sampler_noise_kernel(float* __restrict__ out, const uint32_t* __restrict__ seed, const int* __restrict__ streams,
+                                                            const int* __restrict__ step, int bs, long HW) {
+  const uint32_t k0 = seed[0], k1 = seed[1], st = (uint32_t)*step;
+  const long total = (long)bs * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long smp = i / HW, px = i - smp * HW;
+    float z[4];
+    sampler_noise4((uint32_t)px, st, streams ? (uint32_t)streams[smp] : 0u, k0, k1, z);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) out[(smp * 4 + c) * HW + px] = z[c];
+  }
+}
+
+// Per element, s = sigma of the step, (sd, su, s_noise, -) one row of cd360/sampler.py::euler_ancestral_table (get_ancestral_step evaluated
+// once per schedule on the host):
+//   d0  = cfg_combine<NB>                              x_e = x + (x - d0) / s * (sd - s)           sampling.py:244-248
+//   x'  = (su == 0) ? x_e : x_e + (z * s_noise) * su                                               sampling.py:250-256
+// su is one table scalar, uniform over the launch; no Philox work on a su == 0 row (the last row, and every row for eta = 0).
+__device__ __forceinline__ float euler_ancestral_update(float xv, float d0, float s, float sd, float su, float s_noise, float z, bool noisy) {
+  const float xe = xv + (xv - d0) / s * (sd - s);
+  return noisy ? xe + (z * s_noise) * su : xe;
+}
+
+// x [bs, 4, HW] fp32 IN PLACE; eps as for cfg_euler_step_cl_kernel; tab [nsteps, 4] (column 0 = sigma), anc [nsteps, 4] = (sd, su, s_noise, -)
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_euler_ancestral_step_cl_kernel(float* __restrict__ x, const uint16_t* __restrict__ eps,
+                                                                          const float* __restrict__ tab, const float* __restrict__ anc,
+                                                                          const int* __restrict__ step, const uint32_t* __restrict__ seed,
+                                                                          const int* __restrict__ streams, float scale, float scale_im, int bs,
+                                                                          long HW, int ld) {
+  const int idx = *step;
+  const float s = tab[idx * 4];
+  const float sd = anc[idx * 4], su = anc[idx * 4 + 1], s_noise = anc[idx * 4 + 2];
+  const bool noisy = su != 0.f;
+  const uint32_t k0 = seed[0], k1 = seed[1];
+  const long total = (long)bs * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long smp = i / HW, px = i - smp * HW;
+    const u32x2 eu = *reinterpret_cast<const u32x2*>(eps + ((0 * bs + smp) * HW + px) * ld);
+    u32x2 ei = eu;  // (NB = 2: unused)
+    if constexpr (NB == 3) ei = *reinterpret_cast<const u32x2*>(eps + ((1 * bs + smp) * HW + px) * ld);
+    const u32x2 ec = *reinterpret_cast<const u32x2*>(eps + (((NB - 1) * bs + smp) * HW + px) * ld);
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (noisy) sampler_noise4((uint32_t)px, (uint32_t)idx, streams ? (uint32_t)streams[smp] : 0u, k0, k1, z);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float e_u = (c & 1) ? bf16hi_to_f32(eu[c >> 1]) : bf16lo_to_f32(eu[c >> 1]);
+      const float e_i = (c & 1) ? bf16hi_to_f32(ei[c >> 1]) : bf16lo_to_f32(ei[c >> 1]);
+      const float e_c = (c & 1) ? bf16hi_to_f32(ec[c >> 1]) : bf16lo_to_f32(ec[c >> 1]);
+      const long at = (smp * 4 + c) * HW + px;
+      const float xv = x[at];
+      const float d0 = cfg_combine<NB>(xv, s, e_u, e_i, e_c, scale, scale_im);
+      x[at] = euler_ancestral_update(xv, d0, s, sd, su, s_noise, z[c], noisy);
+    }
+  }
+}
+
+// the un-staged form: x [bs, 4, HW] fp32, eps [NB bs, 4, HW] fp32, sigma [1], anc [4] device tensors -> out [bs, 4, HW]
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_euler_ancestral_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
+                                                                       const float* __restrict__ sigma, const float* __restrict__ anc,
+                                                                       const uint32_t* __restrict__ seed, const int* __restrict__ streams,
+                                                                       const int* __restrict__ step, float scale, float scale_im,
+                                                                       float* __restrict__ out, int bs, long HW) {
+  const float s = *sigma;
+  const float sd = anc[0], su = anc[1], s_noise = anc[2];
+  const bool noisy = su != 0.f;
+  const uint32_t k0 = seed[0], k1 = seed[1], st = (uint32_t)*step;
+  const long total = (long)bs * HW, n = total * 4;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long smp = i / HW, px = i - smp * HW;
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (noisy) sampler_noise4((uint32_t)px, st, streams ? (uint32_t)streams[smp] : 0u, k0, k1, z);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const long at = (smp * 4 + c) * HW + px;
+      const float xv = x[at];
+      const float d0 = cfg_combine<NB>(xv, s, eps[at], NB == 3 ? eps[n + at] : 0.f, eps[(NB - 1) * n + at], scale, scale_im);
+      out[at] = euler_ancestral_update(xv, d0, s, sd, su, s_noise, z[c], noisy);
+    }
+  }
+}
+
 inline unsigned tail_grid(long total) {  // grid-stride kernels: one thread per element up to 65536 workgroups
   const long blocks = (total + 255) / 256;
   return (unsigned)(blocks > 65536 ? 65536 : blocks);
@@ -278,6 +400,62 @@ extern "C" int cd360_cfg_dpmpp2m_step_f32(const void* x, const void* eps, const 
   else
     hipLaunchKernelGGL(cfg_dpmpp2m_step_kernel<3>, dim3(tail_grid(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)eps,
                        (const float*)old, (const float*)sigma, (const float*)mult, scale, scale_im, (float*)out, (float*)old_out, (long)n);
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// include/cd360_stochastic.h.  out [bs, 4, HW] fp32 standard normals; seed: device int64[1]; streams: device int32[bs] or null; step: device
+// int32[1].  HW <= 2^32: the pixel is one 32-bit counter word
+extern "C" int cd360_sampler_noise_f32(void* out, const void* seed, const void* streams, const void* step, int bs, int64_t HW, void* stream) {
+  if (!out || !seed || !step || bs <= 0 || HW <= 0 || HW > ((int64_t)1 << 32)) return CD360_ERR_ARG;
+  if ((uintptr_t)seed % 8 || ((uintptr_t)out | (uintptr_t)step | (uintptr_t)streams) % 4) return CD360_ERR_ARG;
+  hipLaunchKernelGGL(sampler_noise_kernel, dim3(tail_grid((long)bs * HW)), dim3(256), 0, (hipStream_t)stream, (float*)out, (const uint32_t*)seed,
+                     (const int*)streams, (const int*)step, bs, (long)HW);
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// x [bs, 4, HW] fp32, eps [3 bs, 4, HW] fp32 (u | ic | c) or, for a NaN scale_im, [2 bs, 4, HW] (u | c); sigma [1], anc [4] = (sigma_down,
+// sigma_up, s_noise, 0) device tensors; out [bs, 4, HW]: a buffer of its own
+extern "C" int cd360_cfg_euler_ancestral_step_f32(const void* x, const void* eps, const void* sigma, const void* anc, const void* seed,
+                                                  const void* streams, const void* step, float scale, float scale_im, void* out, int bs,
+                                                  int64_t HW, void* stream) {
+  if (!x || !eps || !sigma || !anc || !seed || !step || !out || bs <= 0 || HW <= 0 || HW > ((int64_t)1 << 32)) return CD360_ERR_ARG;
+  if ((uintptr_t)seed % 8 || ((uintptr_t)step | (uintptr_t)streams) % 4) return CD360_ERR_ARG;
+  const bool two = std::isnan(scale_im);
+  const long bytes = (long)bs * 4 * HW * (long)sizeof(float);
+  const uintptr_t po = (uintptr_t)out, pe = (uintptr_t)eps, eb = (uintptr_t)bytes * (two ? 2 : 3);
+  if (overlap(out, x, bytes) || (po < pe + eb && pe < po + (uintptr_t)bytes)) return CD360_ERR_ARG;
+  const long total = (long)bs * HW;
+  if (two)
+    hipLaunchKernelGGL(cfg_euler_ancestral_step_kernel<2>, dim3(tail_grid(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+                       (const float*)eps, (const float*)sigma, (const float*)anc, (const uint32_t*)seed, (const int*)streams, (const int*)step,
+                       scale, 0.f, (float*)out, bs, (long)HW);
+  else
+    hipLaunchKernelGGL(cfg_euler_ancestral_step_kernel<3>, dim3(tail_grid(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+                       (const float*)eps, (const float*)sigma, (const float*)anc, (const uint32_t*)seed, (const int*)streams, (const int*)step,
+                       scale, scale_im, (float*)out, bs, (long)HW);
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// x [bs, 4, HW] fp32 IN PLACE; eps, ld and the NaN scale_im as for cd360_cfg_euler_step_cl; step_tab [nsteps, 4] (sigma = column 0),
+// anc_tab [nsteps, 4] = (sigma_down, sigma_up, s_noise, 0); step = the row of both tables AND the noise counter's step word
+extern "C" int cd360_cfg_euler_ancestral_step_cl(void* x, const void* eps, const void* step_tab, const void* anc_tab, const void* step,
+                                                 const void* seed, const void* streams, float scale, float scale_im, int bs, int64_t HW, int ld,
+                                                 void* stream) {
+  if (!x || !eps || !step_tab || !anc_tab || !step || !seed || bs <= 0 || HW <= 0 || HW > ((int64_t)1 << 32) || ld < 4 || ld % 4)
+    return CD360_ERR_ARG;
+  if ((uintptr_t)eps % 8 || (uintptr_t)seed % 8 || ((uintptr_t)x | (uintptr_t)step | (uintptr_t)streams) % 4) return CD360_ERR_ARG;
+  const long total = (long)bs * HW;
+  if (std::isnan(scale_im))
+    hipLaunchKernelGGL(cfg_euler_ancestral_step_cl_kernel<2>, dim3(tail_grid(total)), dim3(256), 0, (hipStream_t)stream, (float*)x,
+                       (const uint16_t*)eps, (const float*)step_tab, (const float*)anc_tab, (const int*)step, (const uint32_t*)seed,
+                       (const int*)streams, scale, 0.f, bs, (long)HW, ld);
+  else
+    hipLaunchKernelGGL(cfg_euler_ancestral_step_cl_kernel<3>, dim3(tail_grid(total)), dim3(256), 0, (hipStream_t)stream, (float*)x,
+                       (const uint16_t*)eps, (const float*)step_tab, (const float*)anc_tab, (const int*)step, (const uint32_t*)seed,
+                       (const int*)streams, scale, scale_im, bs, (long)HW, ld);
   CD360_LAUNCH_CHECK();
   return CD360_OK;
 }

@@ -1,14 +1,16 @@
 #!/usr/bin/env python
-"""Euler against DPM++ 2M through cd360.job.Sampler: the figures of DESIGN.md's section on the second solver.  Calls the job sampler
-directly (bench.py keeps measuring the Euler headline).
+"""Euler against DPM++ 2M and ancestral Euler through cd360.job.Sampler: the figures of DESIGN.md's sections on the further solvers.  Calls
+the job sampler directly (bench.py keeps measuring the Euler headline).
 
-  --solver euler|dpmpp2m   which tail (euler also runs on a checkout that predates the `solver` argument: --repo PATH imports that checkout)
+  --solver euler|dpmpp2m|euler_a   which tail (euler also runs on a checkout that predates the `solver` argument: --repo PATH imports that
+                           checkout); euler_a: seed 360 on both routes
   --branches 2|3           which guider
   --what deviation         n_steps = 4, all 4 steps at latent 32 / 6 views: the captured job sampler against the un-captured module route
-                           (cd360.sampler's EulerEDMSampler / DPMPP2MSampler + the guider + DiscreteDenoiser around the same UNet, eager),
+                           (cd360.sampler's EulerEDMSampler / DPMPP2MSampler / EulerAncestralSampler + the guider + DiscreteDenoiser around the same UNet, eager),
                            max |difference| / max |module-route latent|: the yardstick and the figure of
-                           tests/test_dpmpp2m_gpu.py::test_dpmpp2m_job_agrees_with_the_uncaptured_module_route
-  --what timing            steady-step replay time of the graph sampler under BOTH solvers in this process (median of --reps replays after
+                           tests/test_dpmpp2m_gpu.py::test_dpmpp2m_job_agrees_with_the_uncaptured_module_route and
+                           tests/test_euler_a_gpu.py::test_euler_a_job_agrees_with_the_uncaptured_module_route
+  --what timing            steady-step replay time of the graph sampler under Euler AND --solver in this process (median of --reps replays after
                            warm-up, interleaved), at --latent / --refs (default 128 / 50)
 Prints one JSON line per figure."""
 import argparse
@@ -18,7 +20,7 @@ import statistics
 import sys
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--solver", default="dpmpp2m", choices=("euler", "dpmpp2m"))
+ap.add_argument("--solver", default="dpmpp2m", choices=("euler", "dpmpp2m", "euler_a"))
 ap.add_argument("--branches", type=int, default=3, choices=(2, 3))
 ap.add_argument("--what", default="deviation", choices=("deviation", "timing"))
 ap.add_argument("--repo", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -35,6 +37,7 @@ from cd360 import sampler as S  # noqa: E402
 
 DEV, BF, NB = "cuda", torch.bfloat16, args.branches
 SCALE_IM = 3.5 if NB == 3 else 0
+SEED = 360
 
 
 def one_pose(p, latent, refs):
@@ -53,6 +56,8 @@ def batch(p, latent, refs):
 
 def make(net, pose, ctx, y, n_steps, solver):
     kw = {} if solver == "euler" else {"solver": solver}  # (a checkout that predates the argument serves Euler)
+    if solver == "euler_a":
+        kw["seed"] = SEED
     return job.Sampler(net, pose, ctx, y, n_steps, scale_im=SCALE_IM, use_graph=True, **kw)
 
 
@@ -69,7 +74,10 @@ def deviation():
     got = job.sample_assigned(smp, [(pose, ctx, y, x0)], steps)[0]
     gcfg = ({"target": "sgm.modules.diffusionmodules.guiders.VanillaCFGImgRef", "params": {"scale": 7.5}} if NB == 2 else
             {"target": "sgm.modules.diffusionmodules.guiders.ScheduledCFGImgTextRef", "params": {"scale": 7.5, "scale_im": 3.5}})
-    mod = (S.EulerEDMSampler if args.solver == "euler" else S.DPMPP2MSampler)(num_steps=steps, guider_config=gcfg, device=DEV)
+    if args.solver == "euler_a":
+        mod = S.EulerAncestralSampler(num_steps=steps, guider_config=gcfg, device=DEV, seed=SEED)
+    else:
+        mod = (S.EulerEDMSampler if args.solver == "euler" else S.DPMPP2MSampler)(num_steps=steps, guider_config=gcfg, device=DEV)
     den = S.DiscreteDenoiser().to(DEV)
     sampling.set_cfg_branches(net, NB)
     sampling.clear_rendered_feat(net)
@@ -82,6 +90,8 @@ def deviation():
         s, sn = sig[i].reshape(1), sig[i + 1].reshape(1)
         if args.solver == "euler":
             x, _ = mod.sampler_step(s, sn, denoiser, x, c, uc)
+        elif args.solver == "euler_a":
+            x = mod.sampler_step(s, sn, denoiser, x, c, uc)
         else:
             x, old = mod.sampler_step(old, None if i == 0 else sig[i - 1].reshape(1), s, sn, denoiser, x, c, uc)
     sampling.clear_rendered_feat(net)
@@ -95,7 +105,7 @@ def timing():
     net = bench.build_model(latent, refs, 50, DEV)
     pose, ctx, y, x0 = batch(0, latent, refs)
     smps = {}
-    for solver in ("euler", "dpmpp2m"):
+    for solver in ("euler", "dpmpp2m" if args.solver == "euler" else args.solver):
         smp = make(net, pose, ctx, y, 50, solver)
         x = smp.step(x0.clone(), 0, alias=True)
         for i in range(1, 4):
