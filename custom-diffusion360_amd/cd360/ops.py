@@ -1514,7 +1514,7 @@ def vae_enc_conv_out(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[tor
 
 
 # ----------------------------------------------------------------------------------------------- rank-r adapters (add_lora=True)
-LOWRANK_RANKS = (16, 32, 64)
+LOWRANK_RANKS = (8, 16, 32, 64)
 _DROPOUT_STATE = {}  # device -> int64 [2] (seed, offset) read by the mask of cd360_lowrank_add_bf16 / cd360_dropout_apply_bf16
 _DROPOUT_DRAW = [0]  # host-side draw index of the current step: every mask drawn in a step gets its own site
 

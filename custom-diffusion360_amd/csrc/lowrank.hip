@@ -1,7 +1,7 @@
 // Rank-r adapter branch of the pose blocks' attention projections (sgm/modules/attention.py:330-347,373-376,421-424: add_lora=True)
 // and the dropout that the reference applies to every adapter output while training.
 //
-//   cd360_lowrank_add_bf16   out[M, N] = base[M, N] + s * keep(key, i, j) * (T[M, r] @ U[N, r]^T),  r in {16, 32, 64}
+//   cd360_lowrank_add_bf16   out[M, N] = base[M, N] + s * keep(key, i, j) * (T[M, r] @ U[N, r]^T),  r in {8, 16, 32, 64}
 //   cd360_dropout_apply_bf16 g[M, N]   = s * keep(key, i, j) * dy[M, N]                           (the mask's backward)
 //   cd360_dropout_tick       advances the mask offset kept in device memory                      (one thread, graph-capturable)
 //
@@ -66,12 +66,15 @@ __global__ __launch_bounds__(64 * kWaves) void lowrank_add_kernel(const uint16_t
   const int c = lane & 31, h = lane >> 5;
   const long m = ((long)blockIdx.x * kWaves + wave) * 32 + c;  // this lane's output row
   const bool row_ok = m < M;
-  // B operand: B[k = 8 h + e][col c] = T[m][16 s + 8 h + e], one 16-byte vector per 16-wide step of r
-  bf16x8 tb[R / 16];
+  // B operand: B[k = 8 h + e][col c] = T[m][16 s + 8 h + e], one 16-byte vector per 16-wide step of r (r = 8: half a step, the lanes
+  // of k = 8 .. 15 hold zeros on both operands and read nothing)
+  constexpr int STEPS = (R + 15) / 16;
+  const bool k_ok = R % 16 == 0 || h == 0;
+  bf16x8 tb[STEPS];
 #pragma unroll
-  for (int s = 0; s < R / 16; ++s) {
+  for (int s = 0; s < STEPS; ++s) {
     u32x4 v;
-    load16(T + m * ldt + 16 * s + 8 * h, row_ok, v);
+    load16(T + m * ldt + 16 * s + 8 * h, row_ok && k_ok, v);
     tb[s] = __builtin_bit_cast(bf16x8, v);
   }
   uint32_t rk = 0;
@@ -89,10 +92,10 @@ __global__ __launch_bounds__(64 * kWaves) void lowrank_add_kernel(const uint16_t
       load16(base + m * ldb + nl, out_ok, b0);
       load16(base + m * ldb + nl + 8, out_ok, b1);
     }
-    const bool u_ok = n0 + urow < N;
+    const bool u_ok = n0 + urow < N && k_ok;
     f32x16 acc = {};
 #pragma unroll
-    for (int s = 0; s < R / 16; ++s) {
+    for (int s = 0; s < STEPS; ++s) {
       u32x4 v;
       load16(U + (long)(n0 + urow) * ldu + 16 * s + 8 * h, u_ok, v);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, v), tb[s], acc, 0, 0, 0);
@@ -188,6 +191,7 @@ extern "C" int cd360_lowrank_add_bf16(const void* base, int64_t ldb, const void*
   if ((M + 32 * kWaves - 1) / (32 * kWaves) > 0x7fffffff) return CD360_ERR_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   switch (r) {
+    case 8: return launch_lowrank<8>(base, ldb, t, ldt, u, ldu, out, ldo, M, N, scale, rng_state, site, thresh, st);
     case 16: return launch_lowrank<16>(base, ldb, t, ldt, u, ldu, out, ldo, M, N, scale, rng_state, site, thresh, st);
     case 32: return launch_lowrank<32>(base, ldb, t, ldt, u, ldu, out, ldo, M, N, scale, rng_state, site, thresh, st);
     case 64: return launch_lowrank<64>(base, ldb, t, ldt, u, ldu, out, ldo, M, N, scale, rng_state, site, thresh, st);

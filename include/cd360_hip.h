@@ -549,7 +549,8 @@ int cd360_row_stats_bf16(const void* x, void* stats, int64_t rows, int C, int64_
  *          r = 32, up weights zero-initialised; :373-376 q / k / v; :421-424 `final = to_out(out) + dropouto(up_o(down_o(out)))`; only the
  *          attn1 / attn2 of image_cross blocks carry them, :775, :500, :511).
  * out[M, N] = base[M, N] + s * keep(i, j) * (T[M, r] @ U[N, r]^T): T = x D^T (the down projection, from cd360_gemm_bf16), U = the up
- * weight [N, r] (nn.Linear layout).  r in {16, 32, 64}; all bf16 with element row strides (multiples of 8, >= the row width), 16-byte
+ * weight [N, r] (nn.Linear layout).  r in {8, 16, 32, 64} (T of rank 8 cannot come from cd360_gemm_bf16, whose N % 16 == 0: the module
+ * route keeps rank-8 adapters on torch); all bf16 with element row strides (multiples of 8, >= the row width), 16-byte
  * aligned pointers, N % 16 == 0: column slices of a q|k|v buffer are addressed in place.  out may alias base; base NULL reads as zero
  * (with base = NULL the same entry is the data gradient dX = dY W of a Linear whose output width r is below the GEMM's K % 64).
  * fp32 MFMA accumulation, rounded to bf16 once after the add.  Dropout: p = 0 means no mask and s = 1; 0 < p < 1 draws keep(i, j) with
