@@ -14,7 +14,7 @@ from typing import Callable, List, Sequence
 
 import torch
 
-from . import shard
+from . import shard, solvers
 
 
 class Sampler:
@@ -33,14 +33,14 @@ class Sampler:
     `noise_streams`: one id per replay row (default: stream 0 everywhere -- all poses of a job share the injected noise, as
     sample.py:290-292 shares the start noise); `reseed` / `set_noise_streams` rewrite the device buffers, no re-capture."""
 
-    SOLVERS = ("euler", "dpmpp2m", "euler_a")
+    SOLVERS = tuple(solvers.SOLVERS)
 
     def __init__(self, net, pose, ctx, y, n_steps, scale=7.5, scale_im=3.5, use_graph=False, prefetch=None, graph_render=True, solver="euler",
                  eta=1.0, s_noise=1.0, seed=0, noise_streams=None):
         from cd360 import sampler as S
         if solver not in self.SOLVERS:
             raise ValueError(f"solver {solver!r}: the job sampler serves {', '.join(self.SOLVERS)}")
-        self.solver = solver
+        self.solver, self._solver = solver, solvers.SOLVERS[solver]  # the name, and what only that solver knows (cd360/solvers.py)
         self.eta, self.s_noise, self.seed, self.noise_streams = eta, s_noise, seed, noise_streams
         self.net, self.pose, self.n_steps = net, pose, n_steps
         if use_graph:  # the graphs read the cameras through ONE buffer this sampler owns (retarget rewrites it in place)
@@ -67,6 +67,7 @@ class Sampler:
         self.ctx, self.y = cond3["crossattn"].contiguous(), cond3["vector"].contiguous()
         self.prefetch = prefetch  # cd360.prefetch.WeightPrefetcher or None: armed around both captures
         self.use_graph, self.graph = use_graph, None
+        self.gi = None  # the device-side step index: _build_state, on the first step
         self.graph_render, self.rgraph = use_graph and graph_render, None  # graph_render=False: the render step launched eagerly (A/B)
         # staged steps (round 6): the captured graphs read every per-step scalar from tables through a device-side step index and start /
         # end on cd360_unet_stage_in / cd360_cfg_euler_step_cl, so a replay holds no torch-issued kernel (cd360.routes.no_stage: the A/B partner);
@@ -112,11 +113,19 @@ class Sampler:
         except (AttributeError, IndexError, TypeError):
             return False
 
+    def _build_state(self, x):
+        """What a step of every route reads on the device besides the latent: the step index gi (_iota holds its values, so setting it is
+        one 4-byte device copy) and the solver's own table and buffers."""
+        self._iota = torch.arange(self.n_steps, dtype=torch.int32, device=x.device)
+        self.gi = torch.zeros(1, dtype=torch.int32, device=x.device)
+        self._solver.build(self, x)
+
     @torch.no_grad()
     def _build_stage(self, x):
         """Per-schedule tables and static buffers of the staged steps: row i = what step i of the trajectory derives from sigma_i alone,
         computed with the denoiser's / the UNet's own modules exactly as the un-staged step computes them inside its graph."""
         from sgm.modules.diffusionmodules.util import timestep_embedding
+        self._build_state(x)
         net, dev, dt = self.net, x.device, self.net.dtype
         rows, tembs = [], []
         for i in range(self.n_steps):
@@ -127,8 +136,6 @@ class Sampler:
             tembs.append(net.time_embed(timestep_embedding(c_noise.expand(self.branches), net.model_channels).to(dt))[0])
         self.step_tab = torch.stack(rows).float().contiguous()
         self.temb_tab = torch.stack(tembs).to(dt).contiguous()
-        self._iota = torch.arange(self.n_steps, dtype=torch.int32, device=dev)
-        self.gi = torch.zeros(1, dtype=torch.int32, device=dev)
         conv = net.input_blocks[0][0]
         self.w36 = conv.weight.detach().float().permute(2, 3, 1, 0).reshape(36, conv.out_channels).contiguous()
         self.b_in = (conv.bias.detach().float() if conv.bias is not None else torch.zeros(conv.out_channels, device=dev)).contiguous()
@@ -136,51 +143,22 @@ class Sampler:
         nbs, (H, W) = self.y.shape[0], x.shape[2:]  # B bs images
         self.h0 = torch.empty(nbs, H * W, conv.out_channels, dtype=dt, device=dev)
         self.emb_act = torch.empty_like(self.lab)
-        if self.solver != "euler":
-            self._build_solver(x)
 
-    def _build_solver(self, x):
-        if self.solver == "euler_a":
-            return self._build_ancestral(x)
-        """DPM++ 2M state: the multiplier table (host fp32, uploaded: the same bits in every sampler of a schedule), the un-staged step's
-        4-float row buffer, and gd = the previous step's denoised latent d0, shaped like gx and shared by both captured graphs.  retarget()
-        does not reset gd: row 0 of the table has m4 = 0 and the kernels then never read it -- which is also why step(x, i) for i > 0 must
-        follow step(., i - 1) of the same image."""
-        from cd360.sampler import dpmpp2m_multipliers
-        self.mult_tab = dpmpp2m_multipliers(self.sigmas).to(x.device)
-        self.gm = self.mult_tab[0].clone()
-        self.gd = torch.zeros_like(x)
-
-    def _build_ancestral(self, x):
-        """Ancestral Euler state: the (sigma_down, sigma_up, s_noise, 0) table (host fp32, uploaded: the same bits in every sampler of a
-        schedule), the un-staged step's 4-float row buffer and its step index, and the generator's seed / stream-id buffers the tail kernels
-        read on the device.  Nothing is carried from one step to the next."""
-        from cd360.sampler import DeviceNoise, euler_ancestral_table, seed_words
-        dev = x.device
-        self.anc_tab = euler_ancestral_table(self.sigmas, self.eta, self.s_noise).to(dev)
-        self.ga = self.anc_tab[0].clone()
-        self.seed_buf = torch.tensor([seed_words(self.seed)], dtype=torch.int64, device=dev)
-        self.streams_buf = torch.zeros(x.shape[0], dtype=torch.int32, device=dev)
-        if self.noise_streams is not None:
-            self.set_noise_streams(self.noise_streams)
-        if getattr(self, "gi", None) is None:  # (the staged step owns gi; the un-staged one gets its own step index)
-            self._iota = torch.arange(self.n_steps, dtype=torch.int32, device=dev)
-            self.gi = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.noise = DeviceNoise(self.seed_buf, self.streams_buf, self.gi)
+    def _need_noise(self):
+        if not self._solver.draws_noise:
+            raise ValueError(f"solver {self.solver!r} draws no noise")
 
     def reseed(self, seed):
         """Another seed for the injected noise: one 8-byte copy into the buffer the captured tails read (no re-capture)."""
         from cd360.sampler import seed_words
-        if self.solver != "euler_a":
-            raise ValueError(f"solver {self.solver!r} draws no noise")
+        self._need_noise()
         self.seed = seed
         if getattr(self, "seed_buf", None) is not None:
             self.seed_buf.copy_(torch.tensor([seed_words(seed)], dtype=torch.int64))
 
     def set_noise_streams(self, ids):
         """One noise stream id per replay row (rows of equal id receive equal noise): copied into the buffer the captured tails read."""
-        if self.solver != "euler_a":
-            raise ValueError(f"solver {self.solver!r} draws no noise")
+        self._need_noise()
         ids = [int(v) for v in ids]
         if len(ids) != self.bs:
             raise ValueError(f"{len(ids)} noise stream ids for {self.bs} replay rows")
@@ -189,41 +167,31 @@ class Sampler:
             self.streams_buf.copy_(torch.tensor(ids, dtype=torch.int32))
 
     def _math_staged(self):
-        """One sampler step on the static buffers, in place on self.gx: stage-in kernel (rep = B) -> UNet trunk -> fused [c_out, CFG, to_d,
-        Euler] kernel reading the output convolution's rows as they lie."""
+        """One sampler step on the static buffers, in place on self.gx: stage-in kernel (rep = B) -> UNet trunk -> the solver's tail kernel
+        (for Euler the fused [c_out, CFG, to_d, Euler]) reading the output convolution's rows as they lie."""
         from cd360 import ops
         H, W = self.gx.shape[2:]
         ops.unet_stage_in(self.gx, self.step_tab, self.gi, self.w36, self.b_in, self.temb_tab, self.lab, self.h0, self.emb_act)
-        eps_cl = self.net.forward_staged(self.h0, self.emb_act, self.ctx, self.pose, H, W)
-        if self.solver == "dpmpp2m":  # x and gd in place: [c_out, CFG, multistep update]
-            return ops.cfg_dpmpp2m_step_cl(self.gx, self.gd, eps_cl, self.step_tab, self.mult_tab, self.gi, self.scale, self.scale_im)
-        if self.solver == "euler_a":  # [c_out, CFG, to_d, Euler to sigma_down, + noise sigma_up]
-            return ops.cfg_euler_ancestral_step_cl(self.gx, eps_cl, self.step_tab, self.anc_tab, self.gi, self.seed_buf, self.streams_buf,
-                                                   self.scale, self.scale_im)
-        return ops.cfg_euler_step_cl(self.gx, eps_cl, self.step_tab, self.gi, self.scale, self.scale_im)
+        return self._solver.tail(self, self.net.forward_staged(self.h0, self.emb_act, self.ctx, self.pose, H, W))
 
-    def _math(self, x, s, s_next, t_unused=None):
-        """One sampler step = guider.prepare_inputs -> DiscreteDenoiser (sigma -> table index, c_in) -> UNet -> fused
-        [c_out, CFG, to_d, Euler] kernel -- or, for DPM++ 2M, the [c_out, CFG, multistep update] kernel on the row in self.gm, which also
-        moves this step's d0 into self.gd; for ancestral Euler the kernel on the row in self.ga and the step index in self.gi."""
-        from cd360.sampler import fused_cfg_dpmpp2m_step, fused_cfg_euler_ancestral_step, fused_cfg_euler_step
-        unet = lambda x_in, c_noise: self.net(x_in, timesteps=c_noise, context=self.ctx, y=self.y, pose=self.pose)[0]  # noqa: E731
-        if self.solver == "dpmpp2m":
-            out, d0 = fused_cfg_dpmpp2m_step(self.denoiser, unet, x, self.gd, s, self.gm, self.guider)
-            self.gd.copy_(d0)
-            return out
-        if self.solver == "euler_a":
-            return fused_cfg_euler_ancestral_step(self.denoiser, unet, x, s, self.ga, self.guider, noise=self.noise)
-        return fused_cfg_euler_step(self.denoiser, unet, x, s, s_next, self.guider)
+    def _unet(self, x_in, c_noise):
+        return self.net(x_in, timesteps=c_noise, context=self.ctx, y=self.y, pose=self.pose)[0]
+
+    def _math(self, x, s, s_next):
+        """One un-staged sampler step = guider.prepare_inputs -> DiscreteDenoiser (sigma -> table index, c_in) -> UNet -> the solver's
+        fused tail kernel (for Euler [c_out, CFG, to_d, Euler]) on the row _set_step wrote."""
+        return self._solver.step(self, self._unet, x, s, s_next)
+
+    def _math_static(self):
+        """The step as both graphs capture it: on the sampler's own buffers."""
+        return self._math_staged() if self.staged else self._math(self.gx, self.gs[0], self.gs[1])
 
     @torch.no_grad()
     def eps(self, x, i):
         """The UNet's output for step i of the schedule (the guider's CFG branches), launched eagerly: what --fp8-attn's tolerance report compares."""
-        nb = self.branches
+        from cd360.sampler import cfg_eps
         self._state_layout()
-        x3 = x.expand(nb, -1, -1, -1) if x.shape[0] == 1 else torch.cat([x] * nb)
-        x_in, c_noise, _, _, _ = self.denoiser.network_inputs(x3, self.sigmas[i].expand(x3.shape[0]), {})
-        return self.net(x_in, timesteps=c_noise, context=self.ctx, y=self.y, pose=self.pose)[0].float()
+        return cfg_eps(self.denoiser, self._unet, x, self.sigmas[i], self.branches).float()
 
     def _pin_rendered(self):
         """Keep every block's cached render in a fixed buffer so a captured graph keeps reading the current image's render."""
@@ -278,7 +246,7 @@ class Sampler:
         from cd360 import sampling
         sampling.clear_rendered_feat(self.net)
         self._state_layout()
-        out = self._math_staged() if self.staged else self._math(self.gx, self.gs[0], self.gs[1], self.gt)
+        out = self._math_static()
         self._pin_rendered()
         return out
 
@@ -288,16 +256,15 @@ class Sampler:
         steady-state step and the render step are each captured once.  Both graphs read / write the same static buffers."""
         if not self.use_graph or self.graph is not None:
             return
-        s, s_next, t = self.sigmas[0], self.sigmas[1], self.sigmas[0:1]
-        self.gx, self.gs, self.gt = x.clone(), torch.stack([s, s_next]), t.clone()
+        self.gx, self.gs = x.clone(), self.sigmas[0:2].clone()
         if self.staged:
             self._build_stage(x)
-        elif self.solver != "euler":
-            self._build_solver(x)
+        else:
+            self._build_state(x)
         self._render()
         if self.staged:
             self.gx.copy_(x)  # (the staged step updates gx in place: captures and warm-ups below start from a sane latent again)
-        self.graph, self.gout = self._capture(self._math_staged if self.staged else (lambda: self._math(self.gx, self.gs[0], self.gs[1], self.gt)))
+        self.graph, self.gout = self._capture(self._math_static)
         if self.graph_render:
             try:
                 self.rgraph, self.rout = self._capture(self._render)
@@ -318,72 +285,54 @@ class Sampler:
         for att, kv in self._pins[1]:
             att._kv_cache = kv
 
+    def _set_step(self, i):
+        """Every per-step buffer write.  Staged: the step index alone (the kernels pick their table rows through it).  Un-staged: the
+        solver's own row and, for the captured step, sigma / sigma_next."""
+        if self.staged:
+            self.gi.copy_(self._iota[i:i + 1])
+            return
+        self._solver.set_row(self, i)
+        if self.use_graph:
+            self.gs[0].copy_(self.sigmas[i])
+            self.gs[1].copy_(self.sigmas[i + 1])
+
     @torch.no_grad()
     def step(self, x, i, alias: bool = False):
         """Step i of the schedule on latent x.  alias=True (the job loop): the result may be the sampler's own latent buffer, valid until
         the next call, and passing it straight back skips the copy-in -- a staged replay is then ONE 4-byte index copy plus the graph."""
         i = i % self.n_steps
-        s, s_next, t = self.sigmas[i], self.sigmas[i + 1], self.sigmas[i:i + 1]
-        if self.staged:
-            # (eager launches run the SAME staged step: the stage-in kernel's input convolution rounds a few outputs to the other bf16
-            # neighbour than the implicit-GEMM kernel does, and 70 random-init blocks amplify that to 1e-2 of eps -- graph and eager
-            # must not differ by it; tests/test_f_rows_gpu.py holds the staged ends against the module arithmetic op by op)
-            if self.use_graph:
-                self.prepare(x)
-            elif getattr(self, "step_tab", None) is None:
+        # (eager launches of a staged sampler run the SAME staged step: the stage-in kernel's input convolution rounds a few outputs to the
+        # other bf16 neighbour than the implicit-GEMM kernel does, and 70 random-init blocks amplify that to 1e-2 of eps -- graph and eager
+        # must not differ by it; tests/test_f_rows_gpu.py holds the staged ends against the module arithmetic op by op)
+        if self.use_graph:
+            self.prepare(x)
+        elif self.gi is None:
+            if self.staged:
                 self.gx = x.clone()
                 self._build_stage(x)
-            if x is not self.gx:
-                self.gx.copy_(x)
-            self.gi.copy_(self._iota[i:i + 1])
-            if not self.use_graph:
-                if i == 0:
-                    from cd360 import sampling
-                    sampling.clear_rendered_feat(self.net)
-                    self._state_layout()
-                self._math_staged()
-            elif i == 0:
-                if self.rgraph is not None:
-                    self.rgraph.replay()
-                    self._restore_pins()
-                else:
-                    self._render()
             else:
-                self.graph.replay()
-            return self.gx if alias else self.gx.clone()
+                self._build_state(x)
+        if (self.staged or self.use_graph) and x is not self.gx:  # these steps run on the sampler's own latent buffer
+            self.gx.copy_(x)
+        self._set_step(i)
         if not self.use_graph:
             if i == 0:
                 from cd360 import sampling
                 sampling.clear_rendered_feat(self.net)  # new image: the render runs again
                 self._state_layout()
-            if self.solver == "dpmpp2m":
-                if getattr(self, "mult_tab", None) is None:
-                    self._build_solver(x)
-                self.gm.copy_(self.mult_tab[i])
-            if self.solver == "euler_a":
-                if getattr(self, "anc_tab", None) is None:
-                    self._build_solver(x)
-                self.ga.copy_(self.anc_tab[i])
-                self.gi.copy_(self._iota[i:i + 1])
-            return self._math(x, s, s_next, t)
-        self.prepare(x)
-        self.gx.copy_(x)
-        if self.solver == "dpmpp2m":
-            self.gm.copy_(self.mult_tab[i])
-        if self.solver == "euler_a":
-            self.ga.copy_(self.anc_tab[i])
-            self.gi.copy_(self._iota[i:i + 1])
-        self.gs[0].copy_(s)
-        self.gs[1].copy_(s_next)
-        self.gt.copy_(t)
-        if i == 0:
-            if self.rgraph is not None:
-                self.rgraph.replay()
-                self._restore_pins()
-                return self.rout.clone()
-            return self._render().clone()
-        self.graph.replay()
-        return self.gout.clone()
+            out = self._math_staged() if self.staged else self._math(x, self.sigmas[i], self.sigmas[i + 1])
+        elif i > 0:
+            self.graph.replay()
+            out = self.gout
+        elif self.rgraph is not None:
+            self.rgraph.replay()
+            self._restore_pins()
+            out = self.rout
+        else:
+            out = self._render()
+        if self.staged:  # out is gx
+            return out if alias else out.clone()
+        return out.clone() if self.use_graph else out
 
 
 def ops_kv8_buffers(k, heads):

@@ -1219,19 +1219,40 @@ def _cfg_branches(scale_im: Optional[float]) -> int:
     return 3
 
 
-def cfg_euler_step(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, scale: float, scale_im: Optional[float]):
-    """x [n,...] fp32, eps [3n,...] fp32 (u | ic | c) or, with scale_im=None, [2n,...] (u | c), sigma / sigma_next 0-d fp32 device tensors
-    -> Euler-updated x (one kernel)."""
-    _need_gpu(x, eps, sigma, sigma_next)
+def _cfg_flat_args(x: torch.Tensor, eps: torch.Tensor, scale_im: Optional[float]) -> float:
+    """What the flat fp32 tails share: x [n,...] and eps [NB n,...] fp32 contiguous, NB from scale_im -> scale_im as the C ABI takes it."""
     nb = _cfg_branches(scale_im)
     if eps.shape[0] != nb * x.shape[0] or eps.numel() != nb * x.numel():
         raise ValueError(f"eps holds {eps.shape[0]} rows of {tuple(eps.shape[1:])}; the {nb}-branch step on x {tuple(x.shape)} needs {nb * x.shape[0]}")
     assert x.dtype == torch.float32 and eps.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
+    return float("nan") if nb == 2 else float(scale_im)
+
+
+def _cfg_cl_args(x: torch.Tensor, eps_cl: torch.Tensor, step_tab: torch.Tensor, step: torch.Tensor, scale_im: Optional[float]):
+    """What the channels-last tails share: x [bs, 4, H, W] fp32 contiguous, eps_cl [NB bs, H W, >= 4] bf16 rows of unit channel stride,
+    step_tab [nsteps, 4] fp32, step int32 -> (bs, H W, the row stride of eps_cl, scale_im as the C ABI takes it)."""
+    nb = _cfg_branches(scale_im)
+    bs = x.shape[0]
+    hw = x.shape[2] * x.shape[3]
+    if eps_cl.shape[0] != nb * bs:
+        raise ValueError(f"eps_cl holds {eps_cl.shape[0]} images; the {nb}-branch step on {bs} latents needs {nb * bs}")
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == 4 and eps_cl.dtype == torch.bfloat16
+    assert eps_cl.shape[1] == hw and eps_cl.shape[2] >= 4 and eps_cl.stride(2) == 1
+    assert step.dtype == torch.int32 and step_tab.dtype == torch.float32 and step_tab.is_contiguous() and step_tab.shape[1] == 4
+    ld = eps_cl.stride(1)
+    assert eps_cl.stride(0) == hw * ld
+    return bs, hw, ld, float("nan") if nb == 2 else float(scale_im)
+
+
+def cfg_euler_step(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, scale: float, scale_im: Optional[float]):
+    """x [n,...] fp32, eps [3n,...] fp32 (u | ic | c) or, with scale_im=None, [2n,...] (u | c), sigma / sigma_next 0-d fp32 device tensors
+    -> Euler-updated x (one kernel)."""
+    _need_gpu(x, eps, sigma, sigma_next)
+    sim = _cfg_flat_args(x, eps, scale_im)
     assert sigma.dtype == torch.float32 and sigma_next.dtype == torch.float32 and sigma.numel() == 1 and sigma_next.numel() == 1
     out = torch.empty_like(x)
-    check(_lib.load().cd360_cfg_euler_step_f32(_ptr(x), _ptr(eps), _ptr(sigma), _ptr(sigma_next), float(scale),
-                                              float("nan") if nb == 2 else float(scale_im), _ptr(out), x.numel(), _stream()),
-          "cd360_cfg_euler_step_f32")
+    check(_lib.load().cd360_cfg_euler_step_f32(_ptr(x), _ptr(eps), _ptr(sigma), _ptr(sigma_next), float(scale), sim, _ptr(out), x.numel(),
+                                              _stream()), "cd360_cfg_euler_step_f32")
     return out
 
 
@@ -1257,17 +1278,9 @@ def cfg_euler_step_cl(x: torch.Tensor, eps_cl: torch.Tensor, step_tab: torch.Ten
     of wider rows is fine: the row stride is passed) or, with scale_im=None, [2 bs, H W, >= 4] (u | c), sigma / sigma_next =
     step_tab[step][0 / 1]  (cd360_cfg_euler_step_cl)."""
     _need_gpu(x, eps_cl, step_tab, step)
-    nb = _cfg_branches(scale_im)
-    bs = x.shape[0]
-    hw = x.shape[2] * x.shape[3]
-    if eps_cl.shape[0] != nb * bs:
-        raise ValueError(f"eps_cl holds {eps_cl.shape[0]} images; the {nb}-branch step on {bs} latents needs {nb * bs}")
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == 4 and eps_cl.dtype == torch.bfloat16
-    assert eps_cl.shape[1] == hw and eps_cl.shape[2] >= 4 and eps_cl.stride(2) == 1
-    ld = eps_cl.stride(1)
-    assert eps_cl.stride(0) == hw * ld
-    check(_lib.load().cd360_cfg_euler_step_cl(_ptr(x), _ptr(eps_cl), _ptr(step_tab), _ptr(step), float(scale),
-                                             float("nan") if nb == 2 else float(scale_im), bs, hw, ld, _stream()), "cd360_cfg_euler_step_cl")
+    bs, hw, ld, sim = _cfg_cl_args(x, eps_cl, step_tab, step, scale_im)
+    check(_lib.load().cd360_cfg_euler_step_cl(_ptr(x), _ptr(eps_cl), _ptr(step_tab), _ptr(step), float(scale), sim, bs, hw, ld, _stream()),
+          "cd360_cfg_euler_step_cl")
     return x
 
 
@@ -1277,16 +1290,12 @@ def cfg_dpmpp2m_step(x: torch.Tensor, eps: torch.Tensor, old: torch.Tensor, sigm
     scale_im=None, [2n,...] (u | c), sigma a 1-element and mult = (m1, m2, m3, m4) a 4-element fp32 device tensor -> (x', d0), both new
     tensors.  `old` is not read when m4 == 0."""
     _need_gpu(x, eps, old, sigma, mult)
-    nb = _cfg_branches(scale_im)
-    if eps.shape[0] != nb * x.shape[0] or eps.numel() != nb * x.numel():
-        raise ValueError(f"eps holds {eps.shape[0]} rows of {tuple(eps.shape[1:])}; the {nb}-branch step on x {tuple(x.shape)} needs {nb * x.shape[0]}")
-    assert x.dtype == torch.float32 and eps.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous()
+    sim = _cfg_flat_args(x, eps, scale_im)
     assert old.dtype == torch.float32 and old.shape == x.shape and old.is_contiguous()
     assert sigma.dtype == torch.float32 and sigma.numel() == 1 and mult.dtype == torch.float32 and mult.numel() == 4 and mult.is_contiguous()
     out, old_out = torch.empty_like(x), torch.empty_like(x)
-    check(_lib.load().cd360_cfg_dpmpp2m_step_f32(_ptr(x), _ptr(eps), _ptr(old), _ptr(sigma), _ptr(mult), float(scale),
-                                                float("nan") if nb == 2 else float(scale_im), _ptr(out), _ptr(old_out), x.numel(), _stream()),
-          "cd360_cfg_dpmpp2m_step_f32")
+    check(_lib.load().cd360_cfg_dpmpp2m_step_f32(_ptr(x), _ptr(eps), _ptr(old), _ptr(sigma), _ptr(mult), float(scale), sim, _ptr(out),
+                                                _ptr(old_out), x.numel(), _stream()), "cd360_cfg_dpmpp2m_step_f32")
     return out, old_out
 
 
@@ -1296,20 +1305,11 @@ def cfg_dpmpp2m_step_cl(x: torch.Tensor, old: torch.Tensor, eps_cl: torch.Tensor
     cfg_euler_step_cl, sigma = step_tab[step][0], (m1, m2, m3, m4) = mult_tab[step]; x <- m1 x - m2 dd, old <- d0.  `old` is not read
     when m4 == 0."""
     _need_gpu(x, old, eps_cl, step_tab, mult_tab, step)
-    nb = _cfg_branches(scale_im)
-    bs = x.shape[0]
-    hw = x.shape[2] * x.shape[3]
-    if eps_cl.shape[0] != nb * bs:
-        raise ValueError(f"eps_cl holds {eps_cl.shape[0]} images; the {nb}-branch step on {bs} latents needs {nb * bs}")
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == 4 and eps_cl.dtype == torch.bfloat16
+    bs, hw, ld, sim = _cfg_cl_args(x, eps_cl, step_tab, step, scale_im)
     assert old.dtype == torch.float32 and old.shape == x.shape and old.is_contiguous()
-    assert eps_cl.shape[1] == hw and eps_cl.shape[2] >= 4 and eps_cl.stride(2) == 1
-    assert step.dtype == torch.int32 and step_tab.dtype == torch.float32 and step_tab.is_contiguous() and step_tab.shape[1] == 4
     assert mult_tab.dtype == torch.float32 and mult_tab.is_contiguous() and mult_tab.shape == step_tab.shape
-    ld = eps_cl.stride(1)
-    assert eps_cl.stride(0) == hw * ld
-    check(_lib.load().cd360_cfg_dpmpp2m_step_cl(_ptr(x), _ptr(old), _ptr(eps_cl), _ptr(step_tab), _ptr(mult_tab), _ptr(step), float(scale),
-                                               float("nan") if nb == 2 else float(scale_im), bs, hw, ld, _stream()), "cd360_cfg_dpmpp2m_step_cl")
+    check(_lib.load().cd360_cfg_dpmpp2m_step_cl(_ptr(x), _ptr(old), _ptr(eps_cl), _ptr(step_tab), _ptr(mult_tab), _ptr(step), float(scale), sim,
+                                               bs, hw, ld, _stream()), "cd360_cfg_dpmpp2m_step_cl")
     return x
 
 
@@ -1336,17 +1336,15 @@ def cfg_euler_ancestral_step(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Te
     4-element fp32 device tensor; the noise is sampler_noise(seed, streams, step, ...), drawn inside the kernel (none when sigma_up == 0)
     -> x', a new tensor."""
     _need_gpu(x, eps, sigma, anc, seed, streams, step)
-    nb = _cfg_branches(scale_im)
-    if eps.shape[0] != nb * x.shape[0] or eps.numel() != nb * x.numel():
-        raise ValueError(f"eps holds {eps.shape[0]} rows of {tuple(eps.shape[1:])}; the {nb}-branch step on x {tuple(x.shape)} needs {nb * x.shape[0]}")
-    assert x.dtype == torch.float32 and eps.dtype == torch.float32 and x.is_contiguous() and eps.is_contiguous() and x.ndim == 4 and x.shape[1] == 4
+    sim = _cfg_flat_args(x, eps, scale_im)
+    assert x.ndim == 4 and x.shape[1] == 4
     assert sigma.dtype == torch.float32 and sigma.numel() == 1 and anc.dtype == torch.float32 and anc.numel() == 4 and anc.is_contiguous()
     bs = x.shape[0]
     _noise_args(seed, streams, step, bs)
     out = torch.empty_like(x)
     check(_lib.load().cd360_cfg_euler_ancestral_step_f32(_ptr(x), _ptr(eps), _ptr(sigma), _ptr(anc), _ptr(seed), _ptr(streams), _ptr(step),
-                                                        float(scale), float("nan") if nb == 2 else float(scale_im), _ptr(out), bs,
-                                                        x.shape[2] * x.shape[3], _stream()), "cd360_cfg_euler_ancestral_step_f32")
+                                                        float(scale), sim, _ptr(out), bs, x.shape[2] * x.shape[3], _stream()),
+          "cd360_cfg_euler_ancestral_step_f32")
     return out
 
 
@@ -1356,21 +1354,12 @@ def cfg_euler_ancestral_step_cl(x: torch.Tensor, eps_cl: torch.Tensor, step_tab:
     for cfg_euler_step_cl, sigma = step_tab[step][0], (sigma_down, sigma_up, s_noise, 0) = anc_tab[step], the noise =
     sampler_noise(seed, streams, step, ...) drawn inside the kernel (none when sigma_up == 0)."""
     _need_gpu(x, eps_cl, step_tab, anc_tab, step, seed, streams)
-    nb = _cfg_branches(scale_im)
-    bs = x.shape[0]
-    hw = x.shape[2] * x.shape[3]
-    if eps_cl.shape[0] != nb * bs:
-        raise ValueError(f"eps_cl holds {eps_cl.shape[0]} images; the {nb}-branch step on {bs} latents needs {nb * bs}")
-    assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == 4 and eps_cl.dtype == torch.bfloat16
-    assert eps_cl.shape[1] == hw and eps_cl.shape[2] >= 4 and eps_cl.stride(2) == 1
-    assert step_tab.dtype == torch.float32 and step_tab.is_contiguous() and step_tab.shape[1] == 4
+    bs, hw, ld, sim = _cfg_cl_args(x, eps_cl, step_tab, step, scale_im)
     assert anc_tab.dtype == torch.float32 and anc_tab.is_contiguous() and anc_tab.shape == step_tab.shape
     _noise_args(seed, streams, step, bs)
-    ld = eps_cl.stride(1)
-    assert eps_cl.stride(0) == hw * ld
     check(_lib.load().cd360_cfg_euler_ancestral_step_cl(_ptr(x), _ptr(eps_cl), _ptr(step_tab), _ptr(anc_tab), _ptr(step), _ptr(seed),
-                                                       _ptr(streams), float(scale), float("nan") if nb == 2 else float(scale_im), bs, hw, ld,
-                                                       _stream()), "cd360_cfg_euler_ancestral_step_cl")
+                                                       _ptr(streams), float(scale), sim, bs, hw, ld, _stream()),
+          "cd360_cfg_euler_ancestral_step_cl")
     return x
 
 

@@ -179,22 +179,20 @@ class IdentityGuider:
 
 
 # ----------------------------------------------------------------------------------------------- sampler
-class EulerEDMSampler:
-    """Euler steps over the sub-sampled sigma schedule, s_churn = 0 (DDIM-equivalent with EpsScaling)   (sampling.py:85-136,314-318).
+class BaseDiffusionSampler:
+    """What every sampler here is built on (sampling.py:23-83): the discretisation, the guider, the set-up of the loop and the guided
+    denoiser call.
 
     `denoiser(x_batched, sigma_batched, cond) -> (denoised, fg_masks, alphas, rgb_list)` is what DiffusionEngine.sample builds
     (sgm/models/diffusion.py:375-401)."""
 
     def __init__(self, discretization_config=None, num_steps: Optional[int] = None, guider_config=None, verbose: bool = False,
-                 device: str = "cuda", s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0):
+                 device: str = "cuda"):
         from sgm.util import instantiate_from_config
-        if s_churn != 0.0:
-            raise NotImplementedError("s_churn > 0 (stochastic sampling) is not used by sample.py")
         self.num_steps = num_steps
         self.discretization = instantiate_from_config(discretization_config) if discretization_config else LegacyDDPMDiscretization()
         self.guider = instantiate_from_config(guider_config) if guider_config else IdentityGuider()
         self.verbose, self.device = verbose, device
-        self.s_churn, self.s_tmin, self.s_tmax, self.s_noise = s_churn, s_tmin, s_tmax, s_noise
 
     def prepare_sampling_loop(self, x, cond, uc=None, num_steps=None):
         sigmas = self.discretization(self.num_steps if num_steps is None else num_steps, device=x.device)
@@ -205,6 +203,17 @@ class EulerEDMSampler:
     def denoise(self, x, denoiser, sigma, cond, uc):
         denoised, _, _, rgb_list = denoiser(*self.guider.prepare_inputs(x, sigma, cond, uc))
         return self.guider(denoised, sigma), rgb_list
+
+
+class EulerEDMSampler(BaseDiffusionSampler):
+    """Euler steps over the sub-sampled sigma schedule, s_churn = 0 (DDIM-equivalent with EpsScaling)   (sampling.py:85-136,314-318)."""
+
+    def __init__(self, discretization_config=None, num_steps: Optional[int] = None, guider_config=None, verbose: bool = False,
+                 device: str = "cuda", s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0):
+        if s_churn != 0.0:
+            raise NotImplementedError("s_churn > 0 (stochastic sampling) is not used by sample.py")
+        super().__init__(discretization_config, num_steps, guider_config, verbose, device)
+        self.s_churn, self.s_tmin, self.s_tmax, self.s_noise = s_churn, s_tmin, s_tmax, s_noise
 
     def sampler_step(self, sigma, next_sigma, denoiser, x, cond, uc=None, gamma=0.0):
         denoised, rgb_list = self.denoise(x, denoiser, sigma, cond, uc)
@@ -221,26 +230,37 @@ class EulerEDMSampler:
     forward = __call__
 
 
+def cfg_branch_count(x: torch.Tensor, eps: torch.Tensor, scale_im: Optional[float]) -> int:
+    """3 (ScheduledCFGImgTextRef: u | ic | c) or, for scale_im=None, 2 (VanillaCFGImgRef: u | c); eps must hold that many rows per latent."""
+    nb = 2 if scale_im is None else 3
+    if eps.shape[0] != nb * x.shape[0]:
+        raise ValueError(f"eps holds {eps.shape[0]} rows; the {nb}-branch step on {x.shape[0]} latents needs {nb * x.shape[0]}")
+    return nb
+
+
+def cfg_combine(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, scale: float, scale_im: Optional[float]) -> torch.Tensor:
+    """d0 of the fused tails in plain torch, in the kernels' order (csrc/sampler_stage.hip::cfg_combine): den_b = x - sigma eps_b, then the
+    guider's combine.  Two branches are the three-branch expression without the image term."""
+    if scale_im is None:
+        e_u, e_c = eps.float().chunk(2)
+        du, dc = x - sigma * e_u, x - sigma * e_c
+        return du + scale * (dc - du)
+    e_u, e_ic, e_c = eps.float().chunk(3)
+    du, dic, dc = x - sigma * e_u, x - sigma * e_ic, x - sigma * e_c
+    return du + scale * (dc - dic) + scale_im * (dic - du)
+
+
 def cfg_euler_update(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, scale: float,
                      scale_im: Optional[float] = None, fused: bool = True) -> torch.Tensor:
     """One fused tail of a CFG Euler step with EpsScaling: x [n,...] fp32, sigma / sigma_next 0-d device tensors, den_b = x - sigma eps_b,
     x' = x + (x - d0) / sigma * (sigma_next - sigma) with
       scale_im a number (ScheduledCFGImgTextRef):  eps [3n,...] (u | ic | c),  d0 = den_u + scale (den_c - den_ic) + scale_im (den_ic - den_u)
       scale_im=None     (VanillaCFGImgRef):        eps [2n,...] (u | c),       d0 = den_u + scale (den_c - den_u)."""
-    nb = 2 if scale_im is None else 3
-    if eps.shape[0] != nb * x.shape[0]:
-        raise ValueError(f"eps holds {eps.shape[0]} rows; the {nb}-branch step on {x.shape[0]} latents needs {nb * x.shape[0]}")
+    cfg_branch_count(x, eps, scale_im)
     if fused and x.is_cuda:
         from . import ops
         return ops.cfg_euler_step(x, eps, sigma, sigma_next, scale, scale_im)
-    if nb == 2:
-        e_u, e_c = eps.float().chunk(2)
-        du, dc = x - sigma * e_u, x - sigma * e_c
-        d0 = du + scale * (dc - du)
-        return x + (x - d0) / sigma * (sigma_next - sigma)
-    e_u, e_ic, e_c = eps.float().chunk(3)
-    den = [x - sigma * e for e in (e_u, e_ic, e_c)]
-    d0 = den[0] + scale * (den[2] - den[1]) + scale_im * (den[1] - den[0])
+    d0 = cfg_combine(x, eps, sigma, scale, scale_im)
     return x + (x - d0) / sigma * (sigma_next - sigma)
 
 
@@ -251,6 +271,14 @@ def guider_scales(guider):
     if isinstance(guider, VanillaCFGImgRef):
         return guider.scale, None
     raise TypeError(f"the fused step serves ScheduledCFGImgTextRef and VanillaCFGImgRef, not {type(guider).__name__}")
+
+
+def cfg_eps(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, sigma: torch.Tensor, branches: int) -> torch.Tensor:
+    """The head every fused step shares: the guider's batch [x] * B (the conditioning batch is assembled once per image), DiscreteDenoiser's
+    network inputs with sigma snapped to the table ON the device, and the network over the CFG batch -> eps [B n, ...]."""
+    xb = x.expand(branches, *x.shape[1:]) if x.shape[0] == 1 else torch.cat([x] * branches)
+    x_in, c_noise, _, _, _ = denoiser.network_inputs(xb, sigma.expand(xb.shape[0]), {})
+    return network(x_in, c_noise)
 
 
 def fused_cfg_euler_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor,
@@ -267,10 +295,7 @@ def fused_cfg_euler_step(denoiser: "DiscreteDenoiser", network: Callable, x: tor
     `network(x_in, c_noise) -> eps [B n, ...]`; sigma / sigma_next 0-d device tensors of the sampler's schedule (table entries, so the
     snapped sigma_q of c_out equals the sigma of to_d, as in the reference's own run).  No host synchronisation anywhere in the step."""
     scale, scale_im = guider_scales(guider)
-    nb = guider.branches
-    xb = x.expand(nb, *x.shape[1:]) if x.shape[0] == 1 else torch.cat([x] * nb)
-    x_in, c_noise, _, _, _ = denoiser.network_inputs(xb, sigma.expand(xb.shape[0]), {})
-    eps = network(x_in, c_noise)
+    eps = cfg_eps(denoiser, network, x, sigma, guider.branches)
     return cfg_euler_update(x, eps.contiguous(), sigma.reshape(1), sigma_next.reshape(1), scale, scale_im, fused=fused)
 
 
@@ -289,7 +314,7 @@ def to_sigma(neg_log_sigma):
     return neg_log_sigma.neg().exp()
 
 
-class DPMPP2MSampler:
+class DPMPP2MSampler(BaseDiffusionSampler):
     """DPM-Solver++(2M): x' = m1 x - m2 dd with dd = denoised on the first step and where sigma_next = 0, (1 + 1/2r) denoised - (1/2r) old_denoised
     otherwise (sampling.py:390-465).  One network evaluation per step, deterministic.
 
@@ -299,15 +324,8 @@ class DPMPP2MSampler:
     returns (x, rgb_list)."""
 
     def __init__(self, discretization_config=None, num_steps: Optional[int] = None, guider_config=None, verbose: bool = False, device: str = "cuda"):
-        from sgm.util import instantiate_from_config
-        self.num_steps = num_steps
-        self.discretization = instantiate_from_config(discretization_config) if discretization_config else LegacyDDPMDiscretization()
-        self.guider = instantiate_from_config(guider_config) if guider_config else IdentityGuider()
-        self.verbose, self.device = verbose, device
+        super().__init__(discretization_config, num_steps, guider_config, verbose, device)
         self.rgb_list = None
-
-    prepare_sampling_loop = EulerEDMSampler.prepare_sampling_loop
-    denoise = EulerEDMSampler.denoise
 
     def get_variables(self, sigma, next_sigma, previous_sigma=None):
         t, t_next = [to_neg_log_sigma(s) for s in (sigma, next_sigma)]
@@ -371,20 +389,11 @@ def cfg_dpmpp2m_update(x: torch.Tensor, eps: torch.Tensor, old: Optional[torch.T
     """One fused tail of a CFG DPM++ 2M step with EpsScaling -> (x', d0): den_b = x - sigma eps_b, d0 = the guider's combine as in
     cfg_euler_update, dd = d0 if m4 == 0 else m3 d0 - m4 old, x' = m1 x - m2 dd; mult = one row of dpmpp2m_multipliers, `old` = the d0 the
     previous step returned (not read when m4 == 0: None is fine there).  fused=False: the same chain in plain torch, in the kernels' order."""
-    nb = 2 if scale_im is None else 3
-    if eps.shape[0] != nb * x.shape[0]:
-        raise ValueError(f"eps holds {eps.shape[0]} rows; the {nb}-branch step on {x.shape[0]} latents needs {nb * x.shape[0]}")
+    cfg_branch_count(x, eps, scale_im)
     if fused and x.is_cuda:
         from . import ops
         return ops.cfg_dpmpp2m_step(x, eps, torch.empty_like(x) if old is None else old, sigma, mult, scale, scale_im)
-    if nb == 2:
-        e_u, e_c = eps.float().chunk(2)
-        du, dc = x - sigma * e_u, x - sigma * e_c
-        d0 = du + scale * (dc - du)
-    else:
-        e_u, e_ic, e_c = eps.float().chunk(3)
-        du, dic, dc = x - sigma * e_u, x - sigma * e_ic, x - sigma * e_c
-        d0 = du + scale * (dc - dic) + scale_im * (dic - du)
+    d0 = cfg_combine(x, eps, sigma, scale, scale_im)
     m1, m2, m3, m4 = mult.reshape(4).unbind()
     dd = d0 if float(m4) == 0.0 else m3 * d0 - m4 * old
     return m1 * x - m2 * dd, d0
@@ -396,10 +405,7 @@ def fused_cfg_dpmpp2m_step(denoiser: "DiscreteDenoiser", network: Callable, x: t
     tail replaced -- x' , d0 = cfg_dpmpp2m_update(x, eps, old, sigma, mult): cd360_cfg_dpmpp2m_step_f32.  `mult` = row i of
     dpmpp2m_multipliers(sigmas) for sigma = sigmas[i]; `old` = the d0 step i - 1 returned.  Returns (x', d0)."""
     scale, scale_im = guider_scales(guider)
-    nb = guider.branches
-    xb = x.expand(nb, *x.shape[1:]) if x.shape[0] == 1 else torch.cat([x] * nb)
-    x_in, c_noise, _, _, _ = denoiser.network_inputs(xb, sigma.expand(xb.shape[0]), {})
-    eps = network(x_in, c_noise)
+    eps = cfg_eps(denoiser, network, x, sigma, guider.branches)
     return cfg_dpmpp2m_update(x, eps.contiguous(), old, sigma.reshape(1), mult, scale, scale_im, fused=fused)
 
 
@@ -432,7 +438,7 @@ class DeviceNoise:
         return ops.sampler_noise(self.seed, self.streams, self.step, x.shape[0], x.shape[2], x.shape[3])
 
 
-class EulerAncestralSampler:
+class EulerAncestralSampler(BaseDiffusionSampler):
     """Ancestral Euler: x_e = x + (x - denoised) / sigma (sigma_down - sigma), then x' = x_e + noise s_noise sigma_up where sigma_next > 0
     (sampling.py:236-273, 340-347).  One network evaluation per step, like EulerEDMSampler; stochastic.
 
@@ -447,18 +453,11 @@ class EulerAncestralSampler:
 
     def __init__(self, eta=1.0, s_noise=1.0, discretization_config=None, num_steps: Optional[int] = None, guider_config=None,
                  verbose: bool = False, device: str = "cuda", seed: Optional[int] = None):
-        from sgm.util import instantiate_from_config
+        super().__init__(discretization_config, num_steps, guider_config, verbose, device)
         self.eta, self.s_noise = eta, s_noise
-        self.num_steps = num_steps
-        self.discretization = instantiate_from_config(discretization_config) if discretization_config else LegacyDDPMDiscretization()
-        self.guider = instantiate_from_config(guider_config) if guider_config else IdentityGuider()
-        self.verbose, self.device = verbose, device
         self.rgb_list = None
         self.seed, self._draws, self._noise = seed, 0, None
         self.noise_sampler = (lambda x: torch.randn_like(x)) if seed is None else self._seeded_noise
-
-    prepare_sampling_loop = EulerEDMSampler.prepare_sampling_loop
-    denoise = EulerEDMSampler.denoise
 
     def _seeded_noise(self, x):
         if not x.is_cuda:
@@ -518,9 +517,7 @@ def cfg_euler_ancestral_update(x: torch.Tensor, eps: torch.Tensor, sigma: torch.
     itself (cd360_cfg_euler_ancestral_step_f32) -- or a tensor z shaped like x (a caller's own draw): the kernel then computes x_e (its
     sigma_up = 0 form) and the given z is added by torch in the kernel's order; not needed when sigma_up == 0.
     fused=False: the same chain in plain torch, in the kernel's order."""
-    nb = 2 if scale_im is None else 3
-    if eps.shape[0] != nb * x.shape[0]:
-        raise ValueError(f"eps holds {eps.shape[0]} rows; the {nb}-branch step on {x.shape[0]} latents needs {nb * x.shape[0]}")
+    cfg_branch_count(x, eps, scale_im)
     if fused and x.is_cuda and isinstance(noise, DeviceNoise):  # (nothing read back: this is the call a captured un-staged step makes)
         from . import ops
         return ops.cfg_euler_ancestral_step(x, eps, sigma, anc_row.reshape(4), noise.seed, noise.streams, noise.step, scale, scale_im)
@@ -534,14 +531,7 @@ def cfg_euler_ancestral_update(x: torch.Tensor, eps: torch.Tensor, sigma: torch.
         x_e = ops.cfg_euler_ancestral_step(x, eps, sigma, torch.stack([sd, torch.zeros_like(su), s_noise, torch.zeros_like(su)]),
                                            dry.seed, None, dry.step, scale, scale_im)
         return x_e + (noise * s_noise) * su if noisy else x_e
-    if nb == 2:
-        e_u, e_c = eps.float().chunk(2)
-        du, dc = x - sigma * e_u, x - sigma * e_c
-        d0 = du + scale * (dc - du)
-    else:
-        e_u, e_ic, e_c = eps.float().chunk(3)
-        du, dic, dc = x - sigma * e_u, x - sigma * e_ic, x - sigma * e_c
-        d0 = du + scale * (dc - dic) + scale_im * (dic - du)
+    d0 = cfg_combine(x, eps, sigma, scale, scale_im)
     x_e = x + (x - d0) / sigma * (sd - sigma)
     if not noisy:
         return x_e
@@ -555,8 +545,5 @@ def fused_cfg_euler_ancestral_step(denoiser: "DiscreteDenoiser", network: Callab
     with the tail replaced -- x' = cfg_euler_ancestral_update(x, eps, sigma, anc_row, noise=noise).  `anc_row` = row i of
     euler_ancestral_table(sigmas, eta, s_noise) for sigma = sigmas[i]; `noise` as cfg_euler_ancestral_update takes it."""
     scale, scale_im = guider_scales(guider)
-    nb = guider.branches
-    xb = x.expand(nb, *x.shape[1:]) if x.shape[0] == 1 else torch.cat([x] * nb)
-    x_in, c_noise, _, _, _ = denoiser.network_inputs(xb, sigma.expand(xb.shape[0]), {})
-    eps = network(x_in, c_noise)
+    eps = cfg_eps(denoiser, network, x, sigma, guider.branches)
     return cfg_euler_ancestral_update(x, eps.contiguous(), sigma.reshape(1), anc_row, scale, scale_im, noise=noise, fused=fused)

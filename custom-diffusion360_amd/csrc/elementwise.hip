@@ -150,45 +150,6 @@ extern "C" int cd360_add_layernorm_bf16(const void* a, const void* b, const void
   return CD360_OK;
 }
 
-// ---- tail of one CFG Euler step: EpsScaling c_out (denoiser.py:41-44, denoiser_scaling.py:26-32), the guider's
-// combine -- ScheduledCFGImgTextRef (guiders.py:111-114, NB = 3: u | ic | c) or VanillaCFGImgRef (guiders.py:144-147, NB = 2: u | c) --,
-// to_d + Euler update (sampling.py:101-106, sampling_utils.py:39-40).  NB = 2 is the NB = 3 expression without the image term. ----
-namespace {
-template <int NB>
-__global__ void cfg_euler_step_kernel(const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ sigma,
-                                      const float* __restrict__ sigma_next, float scale, float scale_im, float* __restrict__ out, long n) {
-  static_assert(NB == 2 || NB == 3, "two or three CFG branches");
-  const float s = *sigma, sn = *sigma_next;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float xv = x[i];
-    float d0;
-    if constexpr (NB == 3) {
-      const float du = xv - s * eps[i], dic = xv - s * eps[n + i], dc = xv - s * eps[2 * n + i];
-      d0 = du + scale * (dc - dic) + scale_im * (dic - du);
-    } else {
-      const float du = xv - s * eps[i], dc = xv - s * eps[n + i];
-      d0 = du + scale * (dc - du);
-    }
-    out[i] = xv + (xv - d0) / s * (sn - s);
-  }
-}
-}  // namespace
-
-// x [n] fp32 latent, sigma / sigma_next: device scalars; eps [3n] fp32 network output (uncond | image-cond | image+text-cond), or, when
-// scale_im is NaN (tested here, on the host: the kernel never sees it), eps [2n] (uncond | image+text-cond)
-extern "C" int cd360_cfg_euler_step_f32(const void* x, const void* eps, const void* sigma, const void* sigma_next, float scale,
-                                        float scale_im, void* out, int64_t n, void* stream) {
-  if (!x || !eps || !sigma || !sigma_next || !out || n <= 0) return CD360_ERR_ARG;
-  if (std::isnan(scale_im))
-    hipLaunchKernelGGL(cfg_euler_step_kernel<2>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)eps,
-                       (const float*)sigma, (const float*)sigma_next, scale, 0.f, (float*)out, (long)n);
-  else
-    hipLaunchKernelGGL(cfg_euler_step_kernel<3>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)eps,
-                       (const float*)sigma, (const float*)sigma_next, scale, scale_im, (float*)out, (long)n);
-  CD360_LAUNCH_CHECK();
-  return CD360_OK;
-}
-
 // ---- backward of the elementwise epilogues (BASELINE config 4: the reference differentiates them through torch autograd) ----------
 namespace {
 

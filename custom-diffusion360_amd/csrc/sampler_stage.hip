@@ -13,6 +13,7 @@
 #include "cd360_common.h"
 
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -90,49 +91,16 @@ __global__ __launch_bounds__(256) void unet_stage_in_kernel(const float* __restr
   }
 }
 
-// x [bs, 4, HW] fp32, updated IN PLACE; eps [NB bs, HW, ld] bf16 channels-last (channels 0..3 of each pixel row; NB = 3: u | ic | c thirds,
-// NB = 2: u | c halves -- no row past image 2 bs - 1 is read)
-template <int NB>
-__global__ __launch_bounds__(256) void cfg_euler_step_cl_kernel(float* __restrict__ x, const uint16_t* __restrict__ eps, const float* __restrict__ tab,
-                                                                const int* __restrict__ step, float scale, float scale_im, int bs, long HW, int ld) {
-  static_assert(NB == 2 || NB == 3, "two or three CFG branches");
-  const int idx = *step;
-  const float s = tab[idx * 4], sn = tab[idx * 4 + 1];
-  const long total = (long)bs * HW;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long smp = i / HW, px = i - smp * HW;
-    const u32x2 eu = *reinterpret_cast<const u32x2*>(eps + ((0 * bs + smp) * HW + px) * ld);
-    u32x2 ei = eu;  // (NB = 2: unused)
-    if constexpr (NB == 3) ei = *reinterpret_cast<const u32x2*>(eps + ((1 * bs + smp) * HW + px) * ld);
-    const u32x2 ec = *reinterpret_cast<const u32x2*>(eps + (((NB - 1) * bs + smp) * HW + px) * ld);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float e_u = (c & 1) ? bf16hi_to_f32(eu[c >> 1]) : bf16lo_to_f32(eu[c >> 1]);
-      const float e_i = (c & 1) ? bf16hi_to_f32(ei[c >> 1]) : bf16lo_to_f32(ei[c >> 1]);
-      const float e_c = (c & 1) ? bf16hi_to_f32(ec[c >> 1]) : bf16lo_to_f32(ec[c >> 1]);
-      float* xp = x + (smp * 4 + c) * HW + px;
-      const float xv = *xp;
-      float d0;  // (the arithmetic and its order: cfg_euler_step_kernel)
-      if constexpr (NB == 3) {
-        const float du = xv - s * e_u, dic = xv - s * e_i, dc = xv - s * e_c;
-        d0 = du + scale * (dc - dic) + scale_im * (dic - du);
-      } else {
-        const float du = xv - s * e_u, dc = xv - s * e_c;
-        d0 = du + scale * (dc - du);
-      }
-      *xp = xv + (xv - d0) / s * (sn - s);
-    }
-  }
-}
 
-// ---- DPM++ 2M (sampling.py:390-465, DPMPP2MSampler.sampler_step) on the same CFG combine: the second-order multistep update in table form.
-// Per element, with s = sigma of the step and (m1, m2, m3, m4) one row of a per-schedule multiplier table (cd360/sampler.py::dpmpp2m_multipliers:
-// get_variables / get_mult evaluated once per schedule on the host, (m3, m4) = (1, 0) for the first step and for sigma_next = 0):
-//   den_b = x - s eps_b;  d0 = the CFG combine of cfg_euler_step_cl_kernel, same order
-//   dd    = (m4 == 0) ? d0 : m3 d0 - m4 old          `old` (the previous step's d0) is NOT read when m4 == 0: on the first step of an image it holds
-//                                                    the previous image's value or uninitialised memory, and 0 * NaN must not reach x
-//   x'    = m1 x - m2 dd;  old' = d0
-// -ffp-contract=off: one fp32 rounding per operation, in this order (tests/test_dpmpp2m_gpu.py holds both kernels to it bit for bit).
+// ---- the tails of one CFG sampling step: EpsScaling c_out (denoiser.py:41-44, denoiser_scaling.py:26-32), the guider's
+// combine -- ScheduledCFGImgTextRef (guiders.py:111-114, NB = 3: u | ic | c) or VanillaCFGImgRef (guiders.py:144-147, NB = 2: u | c) --,
+// then the solver's update.  Every solver has two kernels: the `_cl` form a captured step ends on (x in place, eps = the output convolution's
+// bf16 channels-last rows, per-step scalars from tables through the device-side step index) and the un-staged flat fp32 form.  They share
+// the combine and the eps loads below and differ in one short update function per solver.
+// -ffp-contract=off: one fp32 rounding per operation, in the order written (tests/test_cfg2_gpu.py, test_dpmpp2m_gpu.py and
+// test_euler_a_gpu.py hold every kernel to it bit for bit).
+
+// den_b = x - s eps_b;  d0 = the guider's combine.  NB = 2 is the NB = 3 expression without the image term.
 template <int NB>
 __device__ __forceinline__ float cfg_combine(float xv, float s, float e_u, float e_i, float e_c, float scale, float scale_im) {
   static_assert(NB == 2 || NB == 3, "two or three CFG branches");
@@ -145,6 +113,76 @@ __device__ __forceinline__ float cfg_combine(float xv, float s, float e_u, float
   }
 }
 
+// flat eps [NB n] fp32: branch b of element i at eps[b n + i]
+template <int NB>
+__device__ __forceinline__ float cfg_combine_flat(const float* __restrict__ eps, long n, long i, float xv, float s, float scale, float scale_im) {
+  return cfg_combine<NB>(xv, s, eps[i], NB == 3 ? eps[n + i] : 0.f, eps[(NB - 1) * n + i], scale, scale_im);
+}
+
+// eps [NB bs, HW, ld] bf16 channels-last (channels 0..3 of each pixel row; NB = 3: u | ic | c thirds, NB = 2: u | c halves -- no row past
+// image 2 bs - 1 is read): one pixel's four channels of every branch, as they lie (two bf16 pairs per branch)
+struct EpsRow {
+  u32x2 u, i, c;  // (NB = 2: i = u, unused)
+};
+
+template <int NB>
+__device__ __forceinline__ EpsRow load_eps_row(const uint16_t* __restrict__ eps, int bs, long HW, int ld, long smp, long px) {
+  EpsRow r;
+  r.u = *reinterpret_cast<const u32x2*>(eps + ((0 * bs + smp) * HW + px) * ld);
+  r.i = r.u;
+  if constexpr (NB == 3) r.i = *reinterpret_cast<const u32x2*>(eps + ((1 * bs + smp) * HW + px) * ld);
+  r.c = *reinterpret_cast<const u32x2*>(eps + (((NB - 1) * bs + smp) * HW + px) * ld);
+  return r;
+}
+
+__device__ __forceinline__ float bf16_of(u32x2 v, int c) { return (c & 1) ? bf16hi_to_f32(v[c >> 1]) : bf16lo_to_f32(v[c >> 1]); }
+
+template <int NB>
+__device__ __forceinline__ float cfg_combine_cl(const EpsRow& r, int c, float xv, float s, float scale, float scale_im) {
+  return cfg_combine<NB>(xv, s, bf16_of(r.u, c), bf16_of(r.i, c), bf16_of(r.c, c), scale, scale_im);
+}
+
+// ---- Euler (sampling.py:101-106, sampling_utils.py:39-40: to_d, then the step to sigma_next) ----
+__device__ __forceinline__ float euler_update(float xv, float d0, float s, float sn) { return xv + (xv - d0) / s * (sn - s); }
+
+// x [bs, 4, HW] fp32, updated IN PLACE; eps: see load_eps_row; tab [nsteps, 4] = (sigma, sigma_next, c_in, -)
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_euler_step_cl_kernel(float* __restrict__ x, const uint16_t* __restrict__ eps, const float* __restrict__ tab,
+                                                                const int* __restrict__ step, float scale, float scale_im, int bs, long HW, int ld) {
+  const int idx = *step;
+  const float s = tab[idx * 4], sn = tab[idx * 4 + 1];
+  const long total = (long)bs * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long smp = i / HW, px = i - smp * HW;
+    const EpsRow e = load_eps_row<NB>(eps, bs, HW, ld, smp, px);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float* xp = x + (smp * 4 + c) * HW + px;
+      const float xv = *xp;
+      *xp = euler_update(xv, cfg_combine_cl<NB>(e, c, xv, s, scale, scale_im), s, sn);
+    }
+  }
+}
+
+// the un-staged form: x [n] fp32, eps [NB n] fp32, sigma / sigma_next device scalars -> out [n]
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_euler_step_kernel(const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ sigma,
+                                                             const float* __restrict__ sigma_next, float scale, float scale_im,
+                                                             float* __restrict__ out, long n) {
+  const float s = *sigma, sn = *sigma_next;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float xv = x[i];
+    out[i] = euler_update(xv, cfg_combine_flat<NB>(eps, n, i, xv, s, scale, scale_im), s, sn);
+  }
+}
+
+// ---- DPM++ 2M (sampling.py:390-465, DPMPP2MSampler.sampler_step): the second-order multistep update in table form.
+// Per element, with s = sigma of the step and (m1, m2, m3, m4) one row of a per-schedule multiplier table (cd360/sampler.py::dpmpp2m_multipliers:
+// get_variables / get_mult evaluated once per schedule on the host, (m3, m4) = (1, 0) for the first step and for sigma_next = 0):
+//   d0    = cfg_combine<NB>
+//   dd    = (m4 == 0) ? d0 : m3 d0 - m4 old          `old` (the previous step's d0) is NOT read when m4 == 0: on the first step of an image it holds
+//                                                    the previous image's value or uninitialised memory, and 0 * NaN must not reach x
+//   x'    = m1 x - m2 dd;  old' = d0
 __device__ __forceinline__ float dpmpp2m_update(float xv, float d0, float ov, float m1, float m2, float m3, float m4, bool multi) {
   const float dd = multi ? m3 * d0 - m4 * ov : d0;
   return m1 * xv - m2 * dd;
@@ -162,26 +200,20 @@ __global__ __launch_bounds__(256) void cfg_dpmpp2m_step_cl_kernel(float* __restr
   const long total = (long)bs * HW;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const long smp = i / HW, px = i - smp * HW;
-    const u32x2 eu = *reinterpret_cast<const u32x2*>(eps + ((0 * bs + smp) * HW + px) * ld);
-    u32x2 ei = eu;  // (NB = 2: unused)
-    if constexpr (NB == 3) ei = *reinterpret_cast<const u32x2*>(eps + ((1 * bs + smp) * HW + px) * ld);
-    const u32x2 ec = *reinterpret_cast<const u32x2*>(eps + (((NB - 1) * bs + smp) * HW + px) * ld);
+    const EpsRow e = load_eps_row<NB>(eps, bs, HW, ld, smp, px);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float e_u = (c & 1) ? bf16hi_to_f32(eu[c >> 1]) : bf16lo_to_f32(eu[c >> 1]);
-      const float e_i = (c & 1) ? bf16hi_to_f32(ei[c >> 1]) : bf16lo_to_f32(ei[c >> 1]);
-      const float e_c = (c & 1) ? bf16hi_to_f32(ec[c >> 1]) : bf16lo_to_f32(ec[c >> 1]);
       const long at = (smp * 4 + c) * HW + px;
       const float xv = x[at];
       const float ov = multi ? old[at] : 0.f;
-      const float d0 = cfg_combine<NB>(xv, s, e_u, e_i, e_c, scale, scale_im);
+      const float d0 = cfg_combine_cl<NB>(e, c, xv, s, scale, scale_im);
       x[at] = dpmpp2m_update(xv, d0, ov, m1, m2, m3, m4, multi);
       old[at] = d0;
     }
   }
 }
 
-// the un-staged form: x, old [n] fp32, eps [NB n] fp32 (branch b at eps + b n), sigma [1], mult [4] device tensors -> out, old_out [n]
+// the un-staged form: x, old [n] fp32, eps [NB n] fp32, sigma [1], mult [4] device tensors -> out, old_out [n]
 template <int NB>
 __global__ __launch_bounds__(256) void cfg_dpmpp2m_step_kernel(const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ old,
                                                                const float* __restrict__ sigma, const float* __restrict__ mult, float scale,
@@ -192,7 +224,7 @@ __global__ __launch_bounds__(256) void cfg_dpmpp2m_step_kernel(const float* __re
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const float xv = x[i];
     const float ov = multi ? old[i] : 0.f;
-    const float d0 = cfg_combine<NB>(xv, s, eps[i], NB == 3 ? eps[n + i] : 0.f, eps[(NB - 1) * n + i], scale, scale_im);
+    const float d0 = cfg_combine_flat<NB>(eps, n, i, xv, s, scale, scale_im);
     out[i] = dpmpp2m_update(xv, d0, ov, m1, m2, m3, m4, multi);
     old_out[i] = d0;
   }
@@ -252,11 +284,11 @@ __global__ __launch_bounds__(256) void sampler_noise_kernel(float* __restrict__ 
 
 // Per element, s = sigma of the step, (sd, su, s_noise, -) one row of cd360/sampler.py::euler_ancestral_table (get_ancestral_step evaluated
 // once per schedule on the host):
-//   d0  = cfg_combine<NB>                              x_e = x + (x - d0) / s * (sd - s)           sampling.py:244-248
-//   x'  = (su == 0) ? x_e : x_e + (z * s_noise) * su                                               sampling.py:250-256
+//   d0  = cfg_combine<NB>                              x_e = the Euler step to sd: x + (x - d0) / s * (sd - s)   sampling.py:244-248
+//   x'  = (su == 0) ? x_e : x_e + (z * s_noise) * su                                                             sampling.py:250-256
 // su is one table scalar, uniform over the launch; no Philox work on a su == 0 row (the last row, and every row for eta = 0).
 __device__ __forceinline__ float euler_ancestral_update(float xv, float d0, float s, float sd, float su, float s_noise, float z, bool noisy) {
-  const float xe = xv + (xv - d0) / s * (sd - s);
+  const float xe = euler_update(xv, d0, s, sd);
   return noisy ? xe + (z * s_noise) * su : xe;
 }
 
@@ -275,21 +307,14 @@ __global__ __launch_bounds__(256) void cfg_euler_ancestral_step_cl_kernel(float*
   const long total = (long)bs * HW;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const long smp = i / HW, px = i - smp * HW;
-    const u32x2 eu = *reinterpret_cast<const u32x2*>(eps + ((0 * bs + smp) * HW + px) * ld);
-    u32x2 ei = eu;  // (NB = 2: unused)
-    if constexpr (NB == 3) ei = *reinterpret_cast<const u32x2*>(eps + ((1 * bs + smp) * HW + px) * ld);
-    const u32x2 ec = *reinterpret_cast<const u32x2*>(eps + (((NB - 1) * bs + smp) * HW + px) * ld);
+    const EpsRow e = load_eps_row<NB>(eps, bs, HW, ld, smp, px);
     float z[4] = {0.f, 0.f, 0.f, 0.f};
     if (noisy) sampler_noise4((uint32_t)px, (uint32_t)idx, streams ? (uint32_t)streams[smp] : 0u, k0, k1, z);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const float e_u = (c & 1) ? bf16hi_to_f32(eu[c >> 1]) : bf16lo_to_f32(eu[c >> 1]);
-      const float e_i = (c & 1) ? bf16hi_to_f32(ei[c >> 1]) : bf16lo_to_f32(ei[c >> 1]);
-      const float e_c = (c & 1) ? bf16hi_to_f32(ec[c >> 1]) : bf16lo_to_f32(ec[c >> 1]);
       const long at = (smp * 4 + c) * HW + px;
       const float xv = x[at];
-      const float d0 = cfg_combine<NB>(xv, s, e_u, e_i, e_c, scale, scale_im);
-      x[at] = euler_ancestral_update(xv, d0, s, sd, su, s_noise, z[c], noisy);
+      x[at] = euler_ancestral_update(xv, cfg_combine_cl<NB>(e, c, xv, s, scale, scale_im), s, sd, su, s_noise, z[c], noisy);
     }
   }
 }
@@ -314,20 +339,44 @@ __global__ __launch_bounds__(256) void cfg_euler_ancestral_step_kernel(const flo
     for (int c = 0; c < 4; ++c) {
       const long at = (smp * 4 + c) * HW + px;
       const float xv = x[at];
-      const float d0 = cfg_combine<NB>(xv, s, eps[at], NB == 3 ? eps[n + at] : 0.f, eps[(NB - 1) * n + at], scale, scale_im);
-      out[at] = euler_ancestral_update(xv, d0, s, sd, su, s_noise, z[c], noisy);
+      out[at] = euler_ancestral_update(xv, cfg_combine_flat<NB>(eps, n, at, xv, s, scale, scale_im), s, sd, su, s_noise, z[c], noisy);
     }
   }
 }
 
+// ---- host side of the tails ----
 inline unsigned tail_grid(long total) {  // grid-stride kernels: one thread per element up to 65536 workgroups
   const long blocks = (total + 255) / 256;
   return (unsigned)(blocks > 65536 ? 65536 : blocks);
 }
 
-inline bool overlap(const void* a, const void* b, long bytes) {
+inline bool overlap(const void* a, const void* b, long bytes_a, long bytes_b) {
   const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-  return pa < pb + (uintptr_t)bytes && pb < pa + (uintptr_t)bytes;
+  return pa < pb + (uintptr_t)bytes_b && pb < pa + (uintptr_t)bytes_a;
+}
+
+inline bool overlap(const void* a, const void* b, long bytes) { return overlap(a, b, bytes, bytes); }
+
+// The C ABI takes the two-branch request as a NaN scale_im (include/cd360_hip.h).  It is tested here, on the host: `launch` receives the
+// branch count as a compile-time constant and the scale_im its kernel is to see (0.f for two branches), so no kernel ever sees the NaN.
+template <class Launch>
+inline void launch_for_branches(float scale_im, Launch&& launch) {
+  if (std::isnan(scale_im))
+    launch(std::integral_constant<int, 2>{}, 0.f);
+  else
+    launch(std::integral_constant<int, 3>{}, scale_im);
+}
+
+// what every `_cl` tail asks of its arguments: eps rows of ld >= 4 channels, ld % 4 == 0 (the 320 -> 4 output convolution writes 16-channel
+// rows), 8-byte aligned for the u32x2 loads
+inline bool cl_args_ok(const void* x, const void* eps, const void* step_tab, const void* step, int bs, int64_t HW, int ld) {
+  return x && eps && step_tab && step && bs > 0 && HW > 0 && ld >= 4 && ld % 4 == 0 && (uintptr_t)eps % 8 == 0;
+}
+
+// what every user of the generator asks: seed a device int64, step / streams device int32 (streams may be null), HW <= 2^32: the pixel is
+// one 32-bit counter word
+inline bool noise_args_ok(const void* seed, const void* streams, const void* step, int64_t HW) {
+  return seed && step && (uintptr_t)seed % 8 == 0 && ((uintptr_t)step | (uintptr_t)streams) % 4 == 0 && HW <= ((int64_t)1 << 32);
 }
 
 }  // namespace
@@ -350,19 +399,27 @@ extern "C" int cd360_unet_stage_in(const void* x, const void* step_tab, const vo
   return CD360_OK;
 }
 
-// x [bs, 4, HW] fp32 in place; eps [3 bs, HW, ld] bf16 (ld >= 4, ld % 4 == 0: the 320 -> 4 output convolution writes 16-channel rows), or
-// eps [2 bs, HW, ld] when scale_im is NaN (tested here, on the host: the kernel never sees it)
+// x [n] fp32 latent, sigma / sigma_next: device scalars; eps [3n] fp32 network output (uncond | image-cond | image+text-cond), or, when
+// scale_im is NaN, eps [2n] (uncond | image+text-cond); out [n]
+extern "C" int cd360_cfg_euler_step_f32(const void* x, const void* eps, const void* sigma, const void* sigma_next, float scale,
+                                        float scale_im, void* out, int64_t n, void* stream) {
+  if (!x || !eps || !sigma || !sigma_next || !out || n <= 0) return CD360_ERR_ARG;
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_euler_step_kernel<decltype(nb)::value>, dim3(tail_grid(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+                       (const float*)eps, (const float*)sigma, (const float*)sigma_next, scale, sim, (float*)out, (long)n);
+  });
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// x [bs, 4, HW] fp32 in place; eps [3 bs, HW, ld] bf16, or eps [2 bs, HW, ld] when scale_im is NaN (cl_args_ok)
 extern "C" int cd360_cfg_euler_step_cl(void* x, const void* eps, const void* step_tab, const void* step, float scale, float scale_im, int bs,
                                        int64_t HW, int ld, void* stream) {
-  if (!x || !eps || !step_tab || !step || bs <= 0 || HW <= 0 || ld < 4 || ld % 4) return CD360_ERR_ARG;
-  if ((uintptr_t)eps % 8) return CD360_ERR_ARG;
-  const long total = (long)bs * HW;
-  if (std::isnan(scale_im))
-    hipLaunchKernelGGL(cfg_euler_step_cl_kernel<2>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (float*)x,
-                       (const uint16_t*)eps, (const float*)step_tab, (const int*)step, scale, 0.f, bs, (long)HW, ld);
-  else
-    hipLaunchKernelGGL(cfg_euler_step_cl_kernel<3>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (float*)x,
-                       (const uint16_t*)eps, (const float*)step_tab, (const int*)step, scale, scale_im, bs, (long)HW, ld);
+  if (!cl_args_ok(x, eps, step_tab, step, bs, HW, ld)) return CD360_ERR_ARG;
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_euler_step_cl_kernel<decltype(nb)::value>, dim3(tail_grid((long)bs * HW)), dim3(256), 0, (hipStream_t)stream,
+                       (float*)x, (const uint16_t*)eps, (const float*)step_tab, (const int*)step, scale, sim, bs, (long)HW, ld);
+  });
   CD360_LAUNCH_CHECK();
   return CD360_OK;
 }
@@ -371,16 +428,14 @@ extern "C" int cd360_cfg_euler_step_cl(void* x, const void* eps, const void* ste
 // step_tab [nsteps, 4] (sigma = column 0), mult_tab [nsteps, 4] = (m1, m2, m3, m4)
 extern "C" int cd360_cfg_dpmpp2m_step_cl(void* x, void* old, const void* eps, const void* step_tab, const void* mult_tab, const void* step, float scale,
                                          float scale_im, int bs, int64_t HW, int ld, void* stream) {
-  if (!x || !old || !eps || !step_tab || !mult_tab || !step || bs <= 0 || HW <= 0 || ld < 4 || ld % 4) return CD360_ERR_ARG;
-  if ((uintptr_t)eps % 8 || ((uintptr_t)x | (uintptr_t)old) % 4) return CD360_ERR_ARG;
+  if (!cl_args_ok(x, eps, step_tab, step, bs, HW, ld) || !old || !mult_tab || ((uintptr_t)x | (uintptr_t)old) % 4) return CD360_ERR_ARG;
   const long total = (long)bs * HW;
   if (overlap(x, old, total * 4 * (long)sizeof(float))) return CD360_ERR_ARG;
-  if (std::isnan(scale_im))
-    hipLaunchKernelGGL(cfg_dpmpp2m_step_cl_kernel<2>, dim3(tail_grid(total)), dim3(256), 0, (hipStream_t)stream, (float*)x, (float*)old,
-                       (const uint16_t*)eps, (const float*)step_tab, (const float*)mult_tab, (const int*)step, scale, 0.f, bs, (long)HW, ld);
-  else
-    hipLaunchKernelGGL(cfg_dpmpp2m_step_cl_kernel<3>, dim3(tail_grid(total)), dim3(256), 0, (hipStream_t)stream, (float*)x, (float*)old,
-                       (const uint16_t*)eps, (const float*)step_tab, (const float*)mult_tab, (const int*)step, scale, scale_im, bs, (long)HW, ld);
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_dpmpp2m_step_cl_kernel<decltype(nb)::value>, dim3(tail_grid(total)), dim3(256), 0, (hipStream_t)stream, (float*)x,
+                       (float*)old, (const uint16_t*)eps, (const float*)step_tab, (const float*)mult_tab, (const int*)step, scale, sim, bs,
+                       (long)HW, ld);
+  });
   CD360_LAUNCH_CHECK();
   return CD360_OK;
 }
@@ -394,21 +449,19 @@ extern "C" int cd360_cfg_dpmpp2m_step_f32(const void* x, const void* eps, const 
   if (overlap(x, old, bytes) || overlap(out, old_out, bytes) || overlap(out, x, bytes) || overlap(out, old, bytes) || overlap(old_out, x, bytes) ||
       overlap(old_out, old, bytes))
     return CD360_ERR_ARG;
-  if (std::isnan(scale_im))
-    hipLaunchKernelGGL(cfg_dpmpp2m_step_kernel<2>, dim3(tail_grid(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)eps,
-                       (const float*)old, (const float*)sigma, (const float*)mult, scale, 0.f, (float*)out, (float*)old_out, (long)n);
-  else
-    hipLaunchKernelGGL(cfg_dpmpp2m_step_kernel<3>, dim3(tail_grid(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x, (const float*)eps,
-                       (const float*)old, (const float*)sigma, (const float*)mult, scale, scale_im, (float*)out, (float*)old_out, (long)n);
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_dpmpp2m_step_kernel<decltype(nb)::value>, dim3(tail_grid(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+                       (const float*)eps, (const float*)old, (const float*)sigma, (const float*)mult, scale, sim, (float*)out, (float*)old_out,
+                       (long)n);
+  });
   CD360_LAUNCH_CHECK();
   return CD360_OK;
 }
 
 // include/cd360_stochastic.h.  out [bs, 4, HW] fp32 standard normals; seed: device int64[1]; streams: device int32[bs] or null; step: device
-// int32[1].  HW <= 2^32: the pixel is one 32-bit counter word
+// int32[1] (noise_args_ok)
 extern "C" int cd360_sampler_noise_f32(void* out, const void* seed, const void* streams, const void* step, int bs, int64_t HW, void* stream) {
-  if (!out || !seed || !step || bs <= 0 || HW <= 0 || HW > ((int64_t)1 << 32)) return CD360_ERR_ARG;
-  if ((uintptr_t)seed % 8 || ((uintptr_t)out | (uintptr_t)step | (uintptr_t)streams) % 4) return CD360_ERR_ARG;
+  if (!out || bs <= 0 || HW <= 0 || !noise_args_ok(seed, streams, step, HW) || (uintptr_t)out % 4) return CD360_ERR_ARG;
   hipLaunchKernelGGL(sampler_noise_kernel, dim3(tail_grid((long)bs * HW)), dim3(256), 0, (hipStream_t)stream, (float*)out, (const uint32_t*)seed,
                      (const int*)streams, (const int*)step, bs, (long)HW);
   CD360_LAUNCH_CHECK();
@@ -420,21 +473,14 @@ extern "C" int cd360_sampler_noise_f32(void* out, const void* seed, const void* 
 extern "C" int cd360_cfg_euler_ancestral_step_f32(const void* x, const void* eps, const void* sigma, const void* anc, const void* seed,
                                                   const void* streams, const void* step, float scale, float scale_im, void* out, int bs,
                                                   int64_t HW, void* stream) {
-  if (!x || !eps || !sigma || !anc || !seed || !step || !out || bs <= 0 || HW <= 0 || HW > ((int64_t)1 << 32)) return CD360_ERR_ARG;
-  if ((uintptr_t)seed % 8 || ((uintptr_t)step | (uintptr_t)streams) % 4) return CD360_ERR_ARG;
-  const bool two = std::isnan(scale_im);
+  if (!x || !eps || !sigma || !anc || !out || bs <= 0 || HW <= 0 || !noise_args_ok(seed, streams, step, HW)) return CD360_ERR_ARG;
   const long bytes = (long)bs * 4 * HW * (long)sizeof(float);
-  const uintptr_t po = (uintptr_t)out, pe = (uintptr_t)eps, eb = (uintptr_t)bytes * (two ? 2 : 3);
-  if (overlap(out, x, bytes) || (po < pe + eb && pe < po + (uintptr_t)bytes)) return CD360_ERR_ARG;
-  const long total = (long)bs * HW;
-  if (two)
-    hipLaunchKernelGGL(cfg_euler_ancestral_step_kernel<2>, dim3(tail_grid(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
-                       (const float*)eps, (const float*)sigma, (const float*)anc, (const uint32_t*)seed, (const int*)streams, (const int*)step,
-                       scale, 0.f, (float*)out, bs, (long)HW);
-  else
-    hipLaunchKernelGGL(cfg_euler_ancestral_step_kernel<3>, dim3(tail_grid(total)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
-                       (const float*)eps, (const float*)sigma, (const float*)anc, (const uint32_t*)seed, (const int*)streams, (const int*)step,
-                       scale, scale_im, (float*)out, bs, (long)HW);
+  if (overlap(out, x, bytes) || overlap(out, eps, bytes, bytes * (std::isnan(scale_im) ? 2 : 3))) return CD360_ERR_ARG;
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_euler_ancestral_step_kernel<decltype(nb)::value>, dim3(tail_grid((long)bs * HW)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)x, (const float*)eps, (const float*)sigma, (const float*)anc, (const uint32_t*)seed, (const int*)streams,
+                       (const int*)step, scale, sim, (float*)out, bs, (long)HW);
+  });
   CD360_LAUNCH_CHECK();
   return CD360_OK;
 }
@@ -444,18 +490,13 @@ extern "C" int cd360_cfg_euler_ancestral_step_f32(const void* x, const void* eps
 extern "C" int cd360_cfg_euler_ancestral_step_cl(void* x, const void* eps, const void* step_tab, const void* anc_tab, const void* step,
                                                  const void* seed, const void* streams, float scale, float scale_im, int bs, int64_t HW, int ld,
                                                  void* stream) {
-  if (!x || !eps || !step_tab || !anc_tab || !step || !seed || bs <= 0 || HW <= 0 || HW > ((int64_t)1 << 32) || ld < 4 || ld % 4)
+  if (!cl_args_ok(x, eps, step_tab, step, bs, HW, ld) || !anc_tab || !noise_args_ok(seed, streams, step, HW) || (uintptr_t)x % 4)
     return CD360_ERR_ARG;
-  if ((uintptr_t)eps % 8 || (uintptr_t)seed % 8 || ((uintptr_t)x | (uintptr_t)step | (uintptr_t)streams) % 4) return CD360_ERR_ARG;
-  const long total = (long)bs * HW;
-  if (std::isnan(scale_im))
-    hipLaunchKernelGGL(cfg_euler_ancestral_step_cl_kernel<2>, dim3(tail_grid(total)), dim3(256), 0, (hipStream_t)stream, (float*)x,
-                       (const uint16_t*)eps, (const float*)step_tab, (const float*)anc_tab, (const int*)step, (const uint32_t*)seed,
-                       (const int*)streams, scale, 0.f, bs, (long)HW, ld);
-  else
-    hipLaunchKernelGGL(cfg_euler_ancestral_step_cl_kernel<3>, dim3(tail_grid(total)), dim3(256), 0, (hipStream_t)stream, (float*)x,
-                       (const uint16_t*)eps, (const float*)step_tab, (const float*)anc_tab, (const int*)step, (const uint32_t*)seed,
-                       (const int*)streams, scale, scale_im, bs, (long)HW, ld);
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_euler_ancestral_step_cl_kernel<decltype(nb)::value>, dim3(tail_grid((long)bs * HW)), dim3(256), 0, (hipStream_t)stream,
+                       (float*)x, (const uint16_t*)eps, (const float*)step_tab, (const float*)anc_tab, (const int*)step, (const uint32_t*)seed,
+                       (const int*)streams, scale, sim, bs, (long)HW, ld);
+  });
   CD360_LAUNCH_CHECK();
   return CD360_OK;
 }

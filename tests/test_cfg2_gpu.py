@@ -88,7 +88,8 @@ def _restated(x, e, s, sn, scale, scale_im):
 @pytest.mark.parametrize("scale_im", [3.5, 0.0, -1.25, None])
 def test_both_kernels_equal_a_torch_restatement_in_the_kernels_order(scale_im):
     """Three branches (any finite scale_im, zero and negative included: they stay three-branch calls) and two, both kernels: bit-equal to
-    the expression evaluated operation by operation in fp32 in the documented order -- a changed three-branch instantiation is caught here."""
+    the expression evaluated operation by operation in fp32 in the documented order -- a changed three-branch instantiation is caught here.
+    The two-branch case also runs the `_cl` kernel at 4097 x 4096 pixels, where its grid-stride loop takes a second trip."""
     from cd360 import ops
     nb = 2 if scale_im is None else 3
     g = torch.Generator(device=DEV).manual_seed(11)
@@ -104,6 +105,19 @@ def test_both_kernels_equal_a_torch_restatement_in_the_kernels_order(scale_im):
     x2 = x.clone()
     ops.cfg_euler_step_cl(x2, eps16[..., :4], tab, gi, 7.5, scale_im)
     assert torch.equal(x2, want)
+    if scale_im is None:
+        # one more input, the `_cl` kernel alone: bs = 1, 4097 x 4096 pixels = the first size past 65536 workgroups x 256 threads, so the
+        # grid-stride loop takes a second trip; 4-wide rows (ld = 4).  The restatement is elementwise, so it is evaluated band by band of
+        # 256 image rows and the device holds x, its updated copy and eps only (0.8 GB).
+        H, Wd = 4097, 4096
+        x = torch.randn(1, 4, H, Wd, generator=g, device=DEV)
+        eps4 = torch.randn(2, H * Wd, 4, generator=g, device=DEV, dtype=BF)
+        x2 = x.clone()
+        ops.cfg_euler_step_cl(x2, eps4, tab, gi, 7.5, None)
+        for h0 in range(0, H, 256):
+            h1 = min(h0 + 256, H)
+            e = eps4[:, h0 * Wd:h1 * Wd].float().reshape(2, h1 - h0, Wd, 4).permute(0, 3, 1, 2)
+            assert torch.equal(x2[:, :, h0:h1], _restated(x[:, :, h0:h1], e, s, sn, 7.5, None)), h0
 
 
 # ================================================================================================ 6: guarded runs
