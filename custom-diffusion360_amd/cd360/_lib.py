@@ -126,6 +126,16 @@ STOCHASTIC_SIGNATURES = {
     "cd360_cfg_euler_ancestral_step_cl": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_int, c_int64, c_int, _P]),
 }
 
+# include/cd360_edm.h: churn, and the predictor / corrector tails of the EDM family (EulerEDMSampler with s_churn, HeunEDMSampler).  A fourth
+# table, bound and symbol-checked like the others.
+EDM_SIGNATURES = {
+    "cd360_edm_churn_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int64, _P]),
+    "cd360_cfg_edm_predict_cl": (c_int, [_P, _P, _P, _P, c_float, c_float, _P, _P, c_int, c_int64, c_int, _P]),
+    "cd360_cfg_edm_predict_f32": (c_int, [_P, _P, _P, c_float, c_float, _P, _P, c_int64, _P]),
+    "cd360_cfg_edm_correct_cl": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_int, c_int64, c_int, _P]),
+    "cd360_cfg_edm_correct_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_float, _P, c_int64, _P]),
+}
+
 TUNING_FIELDS = ("gemm_cfg", "gemm_group_m", "gemm_movers", "gemm_ksplit", "conv_cfg", "conv_dma", "conv_kgroup", "conv_wide", "conv_wmajor",
                  "conv_split", "attn_smallk", "attn_smallk_wgs", "attn_self", "attn_fast", "nerf_kernel", "qattn_cfg", "whatif", "gemm_small", "qattn_keys16",
                  "qattn_split", "store_wt", "conv_halo", "gemm_asm4")
@@ -171,7 +181,7 @@ def load(check_symbols: bool = True):
     lib = ctypes.CDLL(LIB_PATH)
     if os.environ.get("CD360_LIB"):
         check_symbols = False  # an explicitly named older / probe build (same-box A/B): entry points it predates stay unbound
-    for name, (res, args) in (*SIGNATURES.items(), *SOLVER_SIGNATURES.items(), *STOCHASTIC_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *SOLVER_SIGNATURES.items(), *STOCHASTIC_SIGNATURES.items(), *EDM_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

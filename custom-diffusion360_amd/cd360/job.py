@@ -31,17 +31,29 @@ class Sampler:
     draws its noise INSIDE the tail kernel as a pure function of (`seed`, the row's noise stream, step index, channel, pixel)
     (include/cd360_stochastic.h), so graph, eager, fresh and un-staged runs add the same bits and no state is kept between steps.
     `noise_streams`: one id per replay row (default: stream 0 everywhere -- all poses of a job share the injected noise, as
-    sample.py:290-292 shares the start noise); `reseed` / `set_noise_streams` rewrite the device buffers, no re-capture."""
+    sample.py:290-292 shares the start noise); `reseed` / `set_noise_streams` rewrite the device buffers, no re-capture.
+    `s_churn` / `s_tmin` / `s_tmax` (with `s_noise`) as EDMSampler's constructor takes them (sampling.py:85-136): with s_churn > 0
+    solver="euler" runs the churned step of include/cd360_edm.h -- noise in front of the UNet on the rows of the window, the UNet at the
+    snapped sigma_hat, the Euler step from sigma_hat -- and `seed` / `noise_streams` / `reseed` / `set_noise_streams` apply to it; with
+    s_churn = 0 it is the step it has always been.  "heun" (HeunEDMSampler, sampling.py:321-337, churn as for Euler) evaluates the UNet
+    twice per step inside ONE captured graph and once on the sigma_next = 0 step, which has a graph of its own; `self.gxe` / `self.gdir`
+    hold the predictor's latent and direction between the two evaluations."""
 
     SOLVERS = tuple(solvers.SOLVERS)
+    EDM_SOLVERS = tuple(k for k in solvers.EDM_SOLVERS if k not in solvers.SOLVERS)  # the names only the EDM registry serves
 
     def __init__(self, net, pose, ctx, y, n_steps, scale=7.5, scale_im=3.5, use_graph=False, prefetch=None, graph_render=True, solver="euler",
-                 eta=1.0, s_noise=1.0, seed=0, noise_streams=None):
+                 eta=1.0, s_noise=1.0, seed=0, noise_streams=None, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf")):
         from cd360 import sampler as S
-        if solver not in self.SOLVERS:
-            raise ValueError(f"solver {solver!r}: the job sampler serves {', '.join(self.SOLVERS)}")
-        self.solver, self._solver = solver, solvers.SOLVERS[solver]  # the name, and what only that solver knows (cd360/solvers.py)
+        if solver not in self.SOLVERS + self.EDM_SOLVERS:
+            raise ValueError(f"solver {solver!r}: the job sampler serves {', '.join(self.SOLVERS + self.EDM_SOLVERS)}")
+        # the name, and what only that solver knows (cd360/solvers.py): the EDM registry serves its own names, and every name it shares with
+        # the first one as soon as the schedule churns
+        edm = solver in solvers.EDM_SOLVERS and (solver not in solvers.SOLVERS or s_churn > 0)
+        self.solver, self._solver = solver, (solvers.EDM_SOLVERS if edm else solvers.SOLVERS)[solver]
         self.eta, self.s_noise, self.seed, self.noise_streams = eta, s_noise, seed, noise_streams
+        self.s_churn, self.s_tmin, self.s_tmax = s_churn, s_tmin, s_tmax
+        self.last_row = False  # True while the step at hand is the sigma_next = 0 step of a solver that shapes it differently (single_last)
         self.net, self.pose, self.n_steps = net, pose, n_steps
         if use_graph:  # the graphs read the cameras through ONE buffer this sampler owns (retarget rewrites it in place)
             from sgm.modules.utils_cameraray import PoseBuffer
@@ -66,7 +78,7 @@ class Sampler:
         _, _, cond3 = self.guider.prepare_inputs(ctx.new_zeros(bs, 1), ctx.new_zeros(bs), c, uc)
         self.ctx, self.y = cond3["crossattn"].contiguous(), cond3["vector"].contiguous()
         self.prefetch = prefetch  # cd360.prefetch.WeightPrefetcher or None: armed around both captures
-        self.use_graph, self.graph = use_graph, None
+        self.use_graph, self.graph, self.lgraph, self._prepared = use_graph, None, None, False
         self.gi = None  # the device-side step index: _build_state, on the first step
         self.graph_render, self.rgraph = use_graph and graph_render, None  # graph_render=False: the render step launched eagerly (A/B)
         # staged steps (round 6): the captured graphs read every per-step scalar from tables through a device-side step index and start /
@@ -124,18 +136,16 @@ class Sampler:
     def _build_stage(self, x):
         """Per-schedule tables and static buffers of the staged steps: row i = what step i of the trajectory derives from sigma_i alone,
         computed with the denoiser's / the UNet's own modules exactly as the un-staged step computes them inside its graph."""
-        from sgm.modules.diffusionmodules.util import timestep_embedding
         self._build_state(x)
         net, dev, dt = self.net, x.device, self.net.dtype
-        rows, tembs = [], []
+        rows, sqs = [], []
         for i in range(self.n_steps):
             sq = self.denoiser.possibly_quantize_sigma(self.sigmas[i].reshape(1))
-            _, _, c_in, c_noise = self.denoiser.scaling(sq)
-            c_noise = self.denoiser.possibly_quantize_c_noise(c_noise)
+            c_in = self.denoiser.scaling(sq)[2]
             rows.append(torch.stack([self.sigmas[i], self.sigmas[i + 1], c_in[0], torch.zeros_like(c_in[0])]))
-            tembs.append(net.time_embed(timestep_embedding(c_noise.expand(self.branches), net.model_channels).to(dt))[0])
+            sqs.append(sq[0])
         self.step_tab = torch.stack(rows).float().contiguous()
-        self.temb_tab = torch.stack(tembs).to(dt).contiguous()
+        self.temb_tab = self.temb_rows(torch.stack(sqs))
         conv = net.input_blocks[0][0]
         self.w36 = conv.weight.detach().float().permute(2, 3, 1, 0).reshape(36, conv.out_channels).contiguous()
         self.b_in = (conv.bias.detach().float() if conv.bias is not None else torch.zeros(conv.out_channels, device=dev)).contiguous()
@@ -143,10 +153,23 @@ class Sampler:
         nbs, (H, W) = self.y.shape[0], x.shape[2:]  # B bs images
         self.h0 = torch.empty(nbs, H * W, conv.out_channels, dtype=dt, device=dev)
         self.emb_act = torch.empty_like(self.lab)
+        self._solver.build_stage(self)
+
+    @torch.no_grad()
+    def temb_rows(self, sq):
+        """A time-embedding table: sq [n] = sigmas ON the denoiser's grid (the schedule's own for temb_tab; a solver's other evaluation
+        points) -> [n, E], row by row through the denoiser's / the UNet's own modules, so equal grid entries give equal bits."""
+        from sgm.modules.diffusionmodules.util import timestep_embedding
+        net, dt = self.net, self.net.dtype
+        tembs = []
+        for i in range(sq.numel()):
+            c_noise = self.denoiser.possibly_quantize_c_noise(self.denoiser.scaling(sq[i].reshape(1))[3])
+            tembs.append(net.time_embed(timestep_embedding(c_noise.expand(self.branches), net.model_channels).to(dt))[0])
+        return torch.stack(tembs).to(dt).contiguous()
 
     def _need_noise(self):
-        if not self._solver.draws_noise:
-            raise ValueError(f"solver {self.solver!r} draws no noise")
+        if not self._solver.draws(self):
+            raise ValueError(f"solver {self.solver!r} with s_churn = {self.s_churn} draws no noise")
 
     def reseed(self, seed):
         """Another seed for the injected noise: one 8-byte copy into the buffer the captured tails read (no re-capture)."""
@@ -166,13 +189,18 @@ class Sampler:
         if getattr(self, "streams_buf", None) is not None:
             self.streams_buf.copy_(torch.tensor(ids, dtype=torch.int32))
 
-    def _math_staged(self):
-        """One sampler step on the static buffers, in place on self.gx: stage-in kernel (rep = B) -> UNet trunk -> the solver's tail kernel
-        (for Euler the fused [c_out, CFG, to_d, Euler]) reading the output convolution's rows as they lie."""
+    def _evaluate(self, x, tab, temb):
+        """One staged network evaluation on latent x: stage-in kernel (rep = B) on the step's row of `tab` / `temb` -> UNet trunk -> the
+        output convolution's rows as they lie."""
         from cd360 import ops
-        H, W = self.gx.shape[2:]
-        ops.unet_stage_in(self.gx, self.step_tab, self.gi, self.w36, self.b_in, self.temb_tab, self.lab, self.h0, self.emb_act)
-        return self._solver.tail(self, self.net.forward_staged(self.h0, self.emb_act, self.ctx, self.pose, H, W))
+        H, W = x.shape[2:]
+        ops.unet_stage_in(x, tab, self.gi, self.w36, self.b_in, temb, self.lab, self.h0, self.emb_act)
+        return self.net.forward_staged(self.h0, self.emb_act, self.ctx, self.pose, H, W)
+
+    def _math_staged(self):
+        """One sampler step on the static buffers, in place on self.gx, as the solver lays it out: for the one-evaluation solvers stage-in
+        on step_tab / temb_tab -> UNet trunk -> the solver's tail kernel (for Euler the fused [c_out, CFG, to_d, Euler])."""
+        return self._solver.staged_step(self, self._evaluate)
 
     def _unet(self, x_in, c_noise):
         return self.net(x_in, timesteps=c_noise, context=self.ctx, y=self.y, pose=self.pose)[0]
@@ -253,18 +281,28 @@ class Sampler:
     @torch.no_grad()
     def prepare(self, x):
         """Untimed set-up of the graph mode: one eager render (builds the per-image tables and the static cache buffers), then the
-        steady-state step and the render step are each captured once.  Both graphs read / write the same static buffers."""
-        if not self.use_graph or self.graph is not None:
+        steady-state step and the render step are each captured once -- and, for a solver whose sigma_next = 0 step has another shape
+        (Heun: one evaluation instead of two), that step a third time.  All graphs read / write the same static buffers."""
+        if not self.use_graph or self._prepared:
             return
+        self._prepared = True
         self.gx, self.gs = x.clone(), self.sigmas[0:2].clone()
         if self.staged:
             self._build_stage(x)
         else:
             self._build_state(x)
+        if self._solver.single_last and self.n_steps == 1:
+            return  # the only step renders AND is the sigma_next = 0 row: launched un-captured
         self._render()
         if self.staged:
             self.gx.copy_(x)  # (the staged step updates gx in place: captures and warm-ups below start from a sane latent again)
         self.graph, self.gout = self._capture(self._math_static)
+        if self._solver.single_last:
+            self.last_row = True
+            try:
+                self.lgraph, self.lout = self._capture(self._math_static)
+            finally:
+                self.last_row = False
         if self.graph_render:
             try:
                 self.rgraph, self.rout = self._capture(self._render)
@@ -315,6 +353,7 @@ class Sampler:
         if (self.staged or self.use_graph) and x is not self.gx:  # these steps run on the sampler's own latent buffer
             self.gx.copy_(x)
         self._set_step(i)
+        self.last_row = last = self._solver.single_last and i == self.n_steps - 1
         if not self.use_graph:
             if i == 0:
                 from cd360 import sampling
@@ -322,9 +361,9 @@ class Sampler:
                 self._state_layout()
             out = self._math_staged() if self.staged else self._math(x, self.sigmas[i], self.sigmas[i + 1])
         elif i > 0:
-            self.graph.replay()
-            out = self.gout
-        elif self.rgraph is not None:
+            (self.lgraph if last else self.graph).replay()
+            out = self.lout if last else self.gout
+        elif self.rgraph is not None and not last:
             self.rgraph.replay()
             self._restore_pins()
             out = self.rout

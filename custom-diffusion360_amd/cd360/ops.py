@@ -1363,6 +1363,82 @@ def cfg_euler_ancestral_step_cl(x: torch.Tensor, eps_cl: torch.Tensor, step_tab:
     return x
 
 
+def _edm_row(row: torch.Tensor):
+    assert row.dtype == torch.float32 and row.numel() == 4 and row.is_contiguous()
+
+
+def edm_churn(x: torch.Tensor, churn_tab: torch.Tensor, step: torch.Tensor, seed: torch.Tensor, streams: Optional[torch.Tensor]):
+    """The churn of an EDM step, IN PLACE on x [bs, 4, H, W] fp32 (cd360_edm_churn_f32, include/cd360_edm.h): x <- x + (z * s_noise) *
+    noise_std with (gamma, noise_std, s_noise, 0) = churn_tab[step] and z = sampler_noise(seed, streams, step, ...) drawn inside the kernel;
+    x is neither read nor written on a noise_std == 0 row."""
+    _need_gpu(x, churn_tab, step, seed, streams)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.ndim == 4 and x.shape[1] == 4
+    assert churn_tab.dtype == torch.float32 and churn_tab.is_contiguous() and churn_tab.ndim == 2 and churn_tab.shape[1] == 4
+    bs = x.shape[0]
+    _noise_args(seed, streams, step, bs)
+    check(_lib.load().cd360_edm_churn_f32(_ptr(x), _ptr(churn_tab), _ptr(step), _ptr(seed), _ptr(streams), bs, x.shape[2] * x.shape[3], _stream()),
+          "cd360_edm_churn_f32")
+    return x
+
+
+def cfg_edm_predict(x: torch.Tensor, eps: torch.Tensor, row: torch.Tensor, scale: float, scale_im: Optional[float], want_dir: bool = True):
+    """The predictor tail of an EDM step (cd360_cfg_edm_predict_f32, include/cd360_edm.h): x [n,...] fp32, eps [3n,...] fp32 (u | ic | c) or,
+    with scale_im=None, [2n,...] (u | c), row = (sigma_hat, sigma_next, c_in, sq) a 4-element fp32 device tensor -> (xe, d), both new
+    tensors: d = (x - d0) / sigma_hat with d0 combined at sq, xe = x + d (sigma_next - sigma_hat).  want_dir=False: d is not written (None)."""
+    _need_gpu(x, eps, row)
+    sim = _cfg_flat_args(x, eps, scale_im)
+    _edm_row(row)
+    xe = torch.empty_like(x)
+    d = torch.empty_like(x) if want_dir else None
+    check(_lib.load().cd360_cfg_edm_predict_f32(_ptr(x), _ptr(eps), _ptr(row), float(scale), sim, _ptr(xe), _ptr(d), x.numel(), _stream()),
+          "cd360_cfg_edm_predict_f32")
+    return xe, d
+
+
+def cfg_edm_predict_cl(x: torch.Tensor, eps_cl: torch.Tensor, edm_tab: torch.Tensor, step: torch.Tensor, scale: float, scale_im: Optional[float],
+                       xe: torch.Tensor, d: Optional[torch.Tensor] = None):
+    """Predictor tail of a captured EDM step (cd360_cfg_edm_predict_cl): x [bs, 4, H, W] fp32 read, eps_cl as for cfg_euler_step_cl,
+    (sigma_hat, sigma_next, -, sq) = edm_tab[step]; xe (may BE x: the in-place, churned Euler tail) and d (or None) are written."""
+    _need_gpu(x, eps_cl, edm_tab, step, xe, d)
+    bs, hw, ld, sim = _cfg_cl_args(x, eps_cl, edm_tab, step, scale_im)
+    for t in (xe,) + (() if d is None else (d,)):
+        assert t.dtype == torch.float32 and t.shape == x.shape and t.is_contiguous()
+    check(_lib.load().cd360_cfg_edm_predict_cl(_ptr(x), _ptr(eps_cl), _ptr(edm_tab), _ptr(step), float(scale), sim, _ptr(xe), _ptr(d), bs, hw, ld,
+                                              _stream()), "cd360_cfg_edm_predict_cl")
+    return xe
+
+
+def cfg_edm_correct(x: torch.Tensor, xe: torch.Tensor, d: torch.Tensor, eps2: torch.Tensor, row: torch.Tensor, corr_row: torch.Tensor, scale: float,
+                    scale_im: Optional[float]):
+    """The Heun corrector tail (cd360_cfg_edm_correct_f32, include/cd360_edm.h): x (the latent the predictor read), xe, d [n,...] fp32, eps2
+    = the network at (xe, sigma_next) [3n,...] or [2n,...] fp32, row / corr_row = one row of edm_tab / corr_tab -> x' = x + (d + d_new) / 2
+    (sigma_next - sigma_hat), a new tensor; xe where sigma_next is not > 0 (eps2 and d are then not read)."""
+    _need_gpu(x, xe, d, eps2, row, corr_row)
+    sim = _cfg_flat_args(x, eps2, scale_im)
+    _edm_row(row)
+    _edm_row(corr_row)
+    for t in (xe, d):
+        assert t.dtype == torch.float32 and t.shape == x.shape and t.is_contiguous()
+    out = torch.empty_like(x)
+    check(_lib.load().cd360_cfg_edm_correct_f32(_ptr(x), _ptr(xe), _ptr(d), _ptr(eps2), _ptr(row), _ptr(corr_row), float(scale), sim, _ptr(out),
+                                               x.numel(), _stream()), "cd360_cfg_edm_correct_f32")
+    return out
+
+
+def cfg_edm_correct_cl(x: torch.Tensor, xe: torch.Tensor, d: torch.Tensor, eps2_cl: torch.Tensor, edm_tab: torch.Tensor, corr_tab: torch.Tensor,
+                       step: torch.Tensor, scale: float, scale_im: Optional[float]):
+    """Corrector tail of a captured Heun step, IN PLACE on x [bs, 4, H, W] fp32 (cd360_cfg_edm_correct_cl): xe, d read, eps2_cl as for
+    cfg_euler_step_cl, (sigma_hat, sigma_next) = edm_tab[step][0 / 1], sq' = corr_tab[step][3]; x <- xe where sigma_next is not > 0."""
+    _need_gpu(x, xe, d, eps2_cl, edm_tab, corr_tab, step)
+    bs, hw, ld, sim = _cfg_cl_args(x, eps2_cl, edm_tab, step, scale_im)
+    for t in (xe, d):
+        assert t.dtype == torch.float32 and t.shape == x.shape and t.is_contiguous()
+    assert corr_tab.dtype == torch.float32 and corr_tab.is_contiguous() and corr_tab.shape == edm_tab.shape
+    check(_lib.load().cd360_cfg_edm_correct_cl(_ptr(x), _ptr(xe), _ptr(d), _ptr(eps2_cl), _ptr(edm_tab), _ptr(corr_tab), _ptr(step), float(scale), sim,
+                                              bs, hw, ld, _stream()), "cd360_cfg_edm_correct_cl")
+    return x
+
+
 def out_conv4_ok(H: int, W: int, cin: int) -> bool:
     return W in (32, 64, 128) and H % 2 == 0 and cin % 64 == 0 and H * W * cin * 2 < 2 ** 31
 

@@ -7,7 +7,7 @@ custom-diffusion360_amd/sgm/modules/diffusionmodules/), so the YAML sampler/deno
 
 Everything stays on the device and nothing synchronises: the sigma -> index quantisation is an argmin + gather on the GPU, and
 with `fused=True` the per-step tail (c_out scaling, 3-way or 2-way CFG combine, to_d, Euler update) is one HIP kernel
-(cd360_cfg_euler_step_f32) instead of ~10 tiny elementwise launches.  DPMPP2MSampler and EulerAncestralSampler are at the end.
+(cd360_cfg_euler_step_f32) instead of ~10 tiny elementwise launches.  DPMPP2MSampler, EulerAncestralSampler and the EDM tables are at the end.
 """
 from __future__ import annotations
 
@@ -206,28 +206,98 @@ class BaseDiffusionSampler:
 
 
 class EulerEDMSampler(BaseDiffusionSampler):
-    """Euler steps over the sub-sampled sigma schedule, s_churn = 0 (DDIM-equivalent with EpsScaling)   (sampling.py:85-136,314-318)."""
+    """Euler steps over the sub-sampled sigma schedule (sampling.py:85-136, 314-318); with s_churn = 0 DDIM-equivalent under EpsScaling.
+
+    s_churn > 0 (sampling.py:96-100, 120-124): on every step whose sigma lies in [s_tmin, s_tmax] the latent is first pushed to
+    sigma_hat = sigma (1 + gamma), gamma = min(s_churn / n_steps, sqrt 2 - 1), by adding noise of standard deviation
+    s_noise (sigma_hat^2 - sigma^2)^0.5; the network is then evaluated at sigma_hat (DiscreteDenoiser snaps it to its grid) and the Euler
+    step runs from sigma_hat.  gamma = 0 keeps the un-churned arithmetic bit for bit (sigma * 1.0 is sigma).
+
+    `noise_sampler`: with seed=None it is torch.randn_like, the reference's draw.  With seed=<int> it is the library's counter-based generator
+    (cd360_sampler_noise_f32: Philox4x32-10 + Box-Muller, stream 0), which is what cd360.job.Sampler(s_churn=..., seed=...) draws inside its
+    captured step: GPU tensors only.  Its step word is the INDEX OF THE STEP since __call__ / prepare_sampling_loop began, counted on every
+    step whether or not it draws (EulerAncestralSampler counts draws: under an s_tmin / s_tmax window the two differ, and the job's
+    kernels read the step index)."""
 
     def __init__(self, discretization_config=None, num_steps: Optional[int] = None, guider_config=None, verbose: bool = False,
-                 device: str = "cuda", s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0):
-        if s_churn != 0.0:
-            raise NotImplementedError("s_churn > 0 (stochastic sampling) is not used by sample.py")
+                 device: str = "cuda", s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, seed: Optional[int] = None):
         super().__init__(discretization_config, num_steps, guider_config, verbose, device)
         self.s_churn, self.s_tmin, self.s_tmax, self.s_noise = s_churn, s_tmin, s_tmax, s_noise
+        self.seed, self._step, self._noise = seed, 0, None
+        self.noise_sampler = (lambda x: torch.randn_like(x)) if seed is None else self._seeded_noise
+
+    def _seeded_noise(self, x):
+        if not x.is_cuda:
+            from ._lib import Cd360Error
+            raise Cd360Error(f"the seeded noise of {type(self).__name__} is drawn by a HIP kernel; got a CPU tensor (seed=None draws torch.randn_like)")
+        if self._noise is None or self._noise.seed.device != x.device:
+            self._noise = DeviceNoise(torch.tensor([seed_words(self.seed)], dtype=torch.int64, device=x.device), None,
+                                      torch.zeros(1, dtype=torch.int32, device=x.device))
+        self._noise.step.fill_(self._step)
+        return self._noise.draw(x)
+
+    def prepare_sampling_loop(self, x, cond, uc=None, num_steps=None):
+        self._step = 0
+        return super().prepare_sampling_loop(x, cond, uc, num_steps)
+
+    def euler_step(self, x, d, dt):
+        return x + dt * d
+
+    def possible_correction_step(self, euler_step, x, d, dt, next_sigma, denoiser, cond, uc):
+        return euler_step
 
     def sampler_step(self, sigma, next_sigma, denoiser, x, cond, uc=None, gamma=0.0):
-        denoised, rgb_list = self.denoise(x, denoiser, sigma, cond, uc)
-        d = (x - denoised) / append_dims(sigma, x.ndim)
-        return x + append_dims(next_sigma - sigma, x.ndim) * d, rgb_list
+        sigma_hat = sigma * (gamma + 1.0)
+        if gamma > 0:
+            eps = self.noise_sampler(x) * self.s_noise
+            x = x + eps * append_dims(sigma_hat ** 2 - sigma ** 2, x.ndim) ** 0.5
+        denoised, rgb_list = self.denoise(x, denoiser, sigma_hat, cond, uc)
+        d = (x - denoised) / append_dims(sigma_hat, x.ndim)
+        dt = append_dims(next_sigma - sigma_hat, x.ndim)
+        euler_step = self.euler_step(x, d, dt)
+        x = self.possible_correction_step(euler_step, x, d, dt, next_sigma, denoiser, cond, uc)
+        self._step += 1
+        return x, rgb_list
+
+    def gamma_of(self, sigma, n_steps):
+        """the reference's per-step gamma (sampling.py:120-124); without churn 0.0 either way, and no sigma is read back from the device"""
+        if not self.s_churn:
+            return 0.0
+        return min(self.s_churn / n_steps, 2 ** 0.5 - 1) if self.s_tmin <= sigma <= self.s_tmax else 0.0
 
     def __call__(self, denoiser: Callable, x, cond: Dict, uc=None, num_steps=None, mask=None, init_im=None):
         x, s_in, sigmas, num_sigmas, cond, uc = self.prepare_sampling_loop(x, cond, uc, num_steps)
         rgb_list = None
         for i in range(num_sigmas - 1):
-            x, rgb_list = self.sampler_step(s_in * sigmas[i], s_in * sigmas[i + 1], denoiser, x, cond, uc)
+            gamma = self.gamma_of(sigmas[i], num_sigmas - 1)
+            x, rgb_list = self.sampler_step(s_in * sigmas[i], s_in * sigmas[i + 1], denoiser, x, cond, uc, gamma)
         return x, rgb_list
 
     forward = __call__
+
+
+class HeunEDMSampler(EulerEDMSampler):
+    """Heun's second-order method on the EDM step (sampling.py:321-337): after the Euler predictor to sigma_next the network is evaluated a
+    second time, at (euler_step, sigma_next), and the step is redone with the mean of the two directions; skipped where sigma_next = 0, so n
+    steps cost 2n - 1 network evaluations.  Same constructor as EulerEDMSampler (churn included); returns (x, rgb_list) with the rgb_list
+    of the step's last `denoise`.
+
+    The reference's class does not run in its own fork as written: BaseDiffusionSampler.denoise returns (denoised, rgb_list) and
+    possible_correction_step uses that tuple as a tensor.  Here `denoise` is unpacked -- the arithmetic is the reference's, operation by
+    operation, including the host-side skip on torch.sum(next_sigma) < 1e-14 and the torch.where on next_sigma > 0."""
+
+    def possible_correction_step(self, euler_step, x, d, dt, next_sigma, denoiser, cond, uc):
+        if torch.sum(next_sigma) < 1e-14:  # save a network evaluation if all noise levels are 0
+            return euler_step
+        denoised, self._rgb2 = self.denoise(euler_step, denoiser, next_sigma, cond, uc)
+        d_new = (euler_step - denoised) / append_dims(next_sigma, euler_step.ndim)
+        d_prime = (d + d_new) / 2.0
+        return torch.where(append_dims(next_sigma, x.ndim) > 0.0, x + d_prime * dt, euler_step)
+
+    def sampler_step(self, sigma, next_sigma, denoiser, x, cond, uc=None, gamma=0.0):
+        self._rgb2 = None
+        x, rgb_list = super().sampler_step(sigma, next_sigma, denoiser, x, cond, uc, gamma)
+        return x, (rgb_list if self._rgb2 is None else self._rgb2)
 
 
 def cfg_branch_count(x: torch.Tensor, eps: torch.Tensor, scale_im: Optional[float]) -> int:
@@ -547,3 +617,125 @@ def fused_cfg_euler_ancestral_step(denoiser: "DiscreteDenoiser", network: Callab
     scale, scale_im = guider_scales(guider)
     eps = cfg_eps(denoiser, network, x, sigma, guider.branches)
     return cfg_euler_ancestral_update(x, eps.contiguous(), sigma.reshape(1), anc_row, scale, scale_im, noise=noise, fused=fused)
+
+
+# ----------------------------------------------------------------------------------------------- EDM with churn, Heun
+def edm_tables(sigmas: torch.Tensor, denoiser: "DiscreteDenoiser", s_churn: float = 0.0, s_tmin: float = 0.0, s_tmax: float = float("inf"),
+               s_noise: float = 1.0):
+    """The per-schedule tables of the EDM family (include/cd360_edm.h): sigmas [n + 1] (the discretisation's output, last = 0) -> three
+    [n, 4] fp32 tables, row i in the reference's own expressions (sampling.py:97-100, 120-124):
+
+        edm_tab    (sigma_hat, sigma_next, c_in(sq), sq)            sq = denoiser.possibly_quantize_sigma(sigma_hat): c_in / c_out / the
+                                                                    time-embedding row come from it, to_d and dt from sigma_hat
+        corr_tab   (sigma_next, sigma_next, c_in(sq'), sq')         sq' = q(sigma_next): the corrector's evaluation (Heun)
+        churn_tab  (gamma, noise_std, s_noise, 0)                   gamma = min(s_churn / n, 2**0.5 - 1) where s_tmin <= sigma_i <= s_tmax, else 0;
+                                                                    sigma_hat = sigma_i * (gamma + 1.0); noise_std = (sigma_hat**2 - sigma_i**2) ** 0.5
+
+    gamma = 0 rows hold noise_std = 0 and sigma_hat = sigma_i exactly.  Computed in CPU fp32 whatever device `sigmas` and the denoiser live
+    on, and uploaded by the caller: graph, eager and fresh samplers share its bits."""
+    sig = sigmas.detach().to("cpu", torch.float32)
+    grid = denoiser.sigmas.detach().to("cpu", torch.float32)
+    n = sig.numel() - 1
+
+    def snapped(s):  # DiscreteDenoiser.possibly_quantize_sigma + EpsScaling's c_in, on the host
+        sq = grid[(s - grid[:, None]).abs().argmin(dim=0).view(s.shape)]
+        return denoiser.scaling(sq)[2], sq
+
+    edm, corr, churn = [], [], []
+    for i in range(n):
+        s, sn = sig[i].reshape(1), sig[i + 1].reshape(1)
+        gamma = min(s_churn / n, 2 ** 0.5 - 1) if s_tmin <= sig[i] <= s_tmax else 0.0
+        s_hat = s * (gamma + 1.0)
+        std = (s_hat ** 2 - s ** 2) ** 0.5 if gamma > 0 else torch.zeros(1)
+        c_in, sq = snapped(s_hat)
+        c_in_n, sq_n = snapped(sn)
+        edm.append(torch.cat([s_hat, sn, c_in, sq]))
+        corr.append(torch.cat([sn, sn, c_in_n, sq_n]))
+        churn.append(torch.cat([torch.full((1,), float(gamma)), std, torch.full((1,), float(s_noise)), torch.zeros(1)]))
+    return torch.stack(edm).contiguous(), torch.stack(corr).contiguous(), torch.stack(churn).contiguous()
+
+
+def edm_churn(x: torch.Tensor, churn: torch.Tensor, noise=None, fused: bool = True) -> torch.Tensor:
+    """The churn in front of an EDM step: x_hat = x + (z * s_noise) * noise_std, x itself where noise_std == 0.  `noise`: a DeviceNoise --
+    fused: ONE kernel that draws z itself (cd360_edm_churn_f32) on a copy of x; `churn` is then the whole churn_tab [n, 4], whose row the
+    kernel picks through noise.step on the device (nothing is read back: the call a captured un-staged step makes) -- or a tensor z shaped
+    like x (a caller's own draw) with `churn` = one row (gamma, noise_std, s_noise, 0), added by torch in the kernel's order; not needed
+    when noise_std == 0.  churn=None: a schedule without churn, x itself."""
+    if churn is None:
+        return x
+    if fused and x.is_cuda and isinstance(noise, DeviceNoise):
+        from . import ops
+        return ops.edm_churn(x.clone(), churn.reshape(-1, 4), noise.step, noise.seed, noise.streams)
+    _, std, s_noise, _ = churn.reshape(4).unbind()
+    if float(std) == 0.0:
+        return x
+    if noise is None:
+        raise ValueError("noise_std != 0: the step needs `noise` (a DeviceNoise or a tensor shaped like x)")
+    z = noise.draw(x) if isinstance(noise, DeviceNoise) else noise
+    return x + (z * s_noise) * std
+
+
+def cfg_edm_predict(x: torch.Tensor, eps: torch.Tensor, edm_row: torch.Tensor, scale: float, scale_im: Optional[float] = None,
+                    fused: bool = True, want_dir: bool = True):
+    """The predictor tail of an EDM step with EpsScaling -> (x_e, d): den_b = x - sq eps_b, d0 = the guider's combine as in cfg_euler_update,
+    d = (x - d0) / sigma_hat, x_e = x + d * (sigma_next - sigma_hat), with (sigma_hat, sigma_next, c_in, sq) = edm_row, one row of
+    edm_tables' first table (cd360_cfg_edm_predict_f32).  want_dir=False: d is None (the churned Euler tail).  fused=False: the same chain
+    in plain torch, in the kernel's order."""
+    cfg_branch_count(x, eps, scale_im)
+    if fused and x.is_cuda:
+        from . import ops
+        return ops.cfg_edm_predict(x, eps, edm_row.reshape(4), scale, scale_im, want_dir=want_dir)
+    sh, sn, _, sq = edm_row.reshape(4).unbind()
+    d = (x - cfg_combine(x, eps, sq, scale, scale_im)) / sh
+    return x + d * (sn - sh), (d if want_dir else None)
+
+
+def cfg_edm_correct(x: torch.Tensor, xe: torch.Tensor, d: torch.Tensor, eps2: torch.Tensor, edm_row: torch.Tensor, corr_row: torch.Tensor,
+                    scale: float, scale_im: Optional[float] = None, fused: bool = True) -> torch.Tensor:
+    """The Heun corrector tail -> x': den_b = x_e - sq' eps2_b, d0' = the guider's combine, d_new = (x_e - d0') / sigma_next, d' = (d + d_new)
+    / 2.0, x' = x + d' * (sigma_next - sigma_hat); x_e where sigma_next is not > 0 (eps2 and d are then not read: None is fine).  x = the
+    latent the predictor read, (x_e, d) its outputs, eps2 = the network at (x_e, sigma_next), sq' = column 3 of corr_row
+    (cd360_cfg_edm_correct_f32).  fused=False: the same chain in plain torch, in the kernel's order."""
+    sh, sn = edm_row.reshape(4)[0], edm_row.reshape(4)[1]
+    if fused and x.is_cuda:
+        from . import ops
+        cfg_branch_count(x, eps2, scale_im)
+        return ops.cfg_edm_correct(x, xe, d, eps2, edm_row.reshape(4), corr_row.reshape(4), scale, scale_im)
+    if not float(sn) > 0.0:
+        return xe.clone()
+    cfg_branch_count(x, eps2, scale_im)
+    d_new = (xe - cfg_combine(xe, eps2, corr_row.reshape(4)[3], scale, scale_im)) / sn
+    return x + (d + d_new) / 2.0 * (sn - sh)
+
+
+def fused_cfg_edm_euler_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, edm_row: torch.Tensor, churn: torch.Tensor, guider,
+                             noise=None, fused: bool = True) -> torch.Tensor:
+    """ONE step of EulerEDMSampler.sampler_step with churn (sampling.py:96-110) in the form the sampling job launches it:
+
+        x_hat = edm_churn(x, churn, noise)                 cd360_edm_churn_f32, in front of the network
+        eps   = network(c_in(sq) [x_hat] * B, idx(sq))     DiscreteDenoiser.network_inputs snaps sigma_hat ON the device
+        x'    = cfg_edm_predict(x_hat, eps, edm_row)[0]    cd360_cfg_edm_predict_f32: c_out at sq, to_d and dt at sigma_hat
+
+    `edm_row` = row i of edm_tables(...)[0]; `churn` and `noise` as edm_churn takes them."""
+    scale, scale_im = guider_scales(guider)
+    x_hat = edm_churn(x, churn, noise, fused=fused)
+    eps = cfg_eps(denoiser, network, x_hat, edm_row.reshape(4)[0], guider.branches)
+    return cfg_edm_predict(x_hat, eps.contiguous(), edm_row, scale, scale_im, fused=fused, want_dir=False)[0]
+
+
+def fused_cfg_heun_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, edm_row: torch.Tensor, corr_row: torch.Tensor,
+                        churn: torch.Tensor, guider, noise=None, fused: bool = True, last: Optional[bool] = None) -> torch.Tensor:
+    """ONE step of HeunEDMSampler.sampler_step (sampling.py:96-110, 321-337) in the form the sampling job launches it:
+    fused_cfg_edm_euler_step keeping d, then -- unless `last` -- a second network evaluation at (x_e, sigma_next) and
+    cfg_edm_correct(x_hat, x_e, d, eps2, edm_row, corr_row): cd360_cfg_edm_correct_f32.  `last`: the host-side skip of the reference
+    (sigma_next < 1e-14); None reads it from edm_row (one read-back: a captured step passes the flag)."""
+    scale, scale_im = guider_scales(guider)
+    x_hat = edm_churn(x, churn, noise, fused=fused)
+    eps = cfg_eps(denoiser, network, x_hat, edm_row.reshape(4)[0], guider.branches)
+    xe, d = cfg_edm_predict(x_hat, eps.contiguous(), edm_row, scale, scale_im, fused=fused)
+    if last is None:
+        last = float(edm_row.reshape(4)[1]) < 1e-14
+    if last:
+        return xe
+    eps2 = cfg_eps(denoiser, network, xe, corr_row.reshape(4)[0], guider.branches)
+    return cfg_edm_correct(x_hat, xe, d, eps2.contiguous(), edm_row, corr_row, scale, scale_im, fused=fused)

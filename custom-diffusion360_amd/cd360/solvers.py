@@ -1,7 +1,9 @@
 """What each solver of cd360.job.Sampler knows and the others do not: its per-schedule table and buffers, the row it writes per step on the
 un-staged route, the tail kernel that ends a staged step, its un-staged step, and whether it draws noise.  One stateless object per
-solver; the state lives on the Sampler `smp` they are handed (smp.mult_tab, smp.gd, smp.anc_tab, smp.seed_buf, smp.streams_buf: the
-names tests and tools read), next to the buffers every solver shares (smp.gx, smp.gi, smp._iota, smp.step_tab)."""
+solver; the state lives on the Sampler `smp` they are handed (smp.mult_tab, smp.gd, smp.anc_tab, smp.seed_buf, smp.streams_buf, smp.edm_tab,
+smp.corr_tab, smp.churn_tab, smp.gxe, smp.gdir: the names tests and tools read), next to the buffers every solver shares (smp.gx, smp.gi,
+smp._iota, smp.step_tab).  SOLVERS holds the one-evaluation solvers on the step table; EDM_SOLVERS the EDM family on its own tables
+(include/cd360_edm.h): Heun, and the Euler step of a schedule that churns."""
 from __future__ import annotations
 
 import torch
@@ -10,16 +12,33 @@ from . import ops
 from . import sampler as S
 
 
-class Euler:
-    """EulerEDMSampler (sampling.py:85-136): sigma and sigma_next are all a step needs."""
+class Solver:
+    """What the job asks of every solver; the defaults are those of a solver with one network evaluation per step, no table of its own and
+    no noise."""
 
     draws_noise = False
+    single_last = False  # True: the sigma_next = 0 step differs in SHAPE from the others (fewer evaluations) and is captured on its own
+
+    def draws(self, smp) -> bool:
+        return self.draws_noise
 
     def build(self, smp, x):
         pass
 
+    def build_stage(self, smp):
+        """Staged route only, after the sampler's own tables exist: further stage-in tables."""
+
     def set_row(self, smp, i):
         pass
+
+    def staged_step(self, smp, evaluate):
+        """One staged step in place on smp.gx.  `evaluate(x, tab, temb)` = stage-in on x with the step's row of `tab` / `temb` -> UNet trunk
+        -> the output convolution's rows."""
+        return self.tail(smp, evaluate(smp.gx, smp.step_tab, smp.temb_tab))
+
+
+class Euler(Solver):
+    """EulerEDMSampler (sampling.py:85-136) with s_churn = 0: sigma and sigma_next are all a step needs."""
 
     def tail(self, smp, eps_cl):  # [c_out, CFG, to_d, Euler]
         return ops.cfg_euler_step_cl(smp.gx, eps_cl, smp.step_tab, smp.gi, smp.scale, smp.scale_im)
@@ -28,10 +47,8 @@ class Euler:
         return S.fused_cfg_euler_step(smp.denoiser, unet, x, s, s_next, smp.guider)
 
 
-class DPMPP2M:
+class DPMPP2M(Solver):
     """DPMPP2MSampler (sampling.py:390-465: second order, multistep, the same one UNet evaluation per step)."""
-
-    draws_noise = False
 
     def build(self, smp, x):
         """The multiplier table (host fp32, uploaded: the same bits in every sampler of a schedule), the un-staged step's 4-float row
@@ -54,7 +71,7 @@ class DPMPP2M:
         return out
 
 
-class EulerAncestral:
+class EulerAncestral(Solver):
     """EulerAncestralSampler (sampling.py:236-273, 340-347: stochastic; smp.eta / smp.s_noise as the reference's constructor takes them)."""
 
     draws_noise = True
@@ -85,3 +102,87 @@ class EulerAncestral:
 
 
 SOLVERS = {"euler": Euler(), "dpmpp2m": DPMPP2M(), "euler_a": EulerAncestral()}
+
+
+class ChurnedEuler(Solver):
+    """EulerEDMSampler with s_churn > 0 (sampling.py:96-136): noise in front of the network on the rows of the s_tmin / s_tmax window, the
+    network at q(sigma_hat), the Euler step from the un-snapped sigma_hat (include/cd360_edm.h).  smp.s_churn / s_tmin / s_tmax / s_noise as
+    the reference's constructor takes them."""
+
+    def draws(self, smp) -> bool:
+        return smp.s_churn > 0
+
+    def build(self, smp, x):
+        """The three tables of cd360.sampler.edm_tables (host fp32, uploaded: the same bits in every sampler of a schedule; c_in re-derived
+        on the device from the uploaded snapped sigma, so an un-churned row is step_tab's row bit for bit), the un-staged
+        step's 4-float row buffers and, where the schedule churns, the generator's seed / stream-id buffers the churn kernel reads on the
+        device.  Nothing is carried from one step to the next."""
+        dev = x.device
+        smp.edm_tab, smp.corr_tab, smp.churn_tab = (t.to(dev) for t in S.edm_tables(smp.sigmas, smp.denoiser, smp.s_churn, smp.s_tmin,
+                                                                                      smp.s_tmax, smp.s_noise))
+        for tab in (smp.edm_tab, smp.corr_tab):  # c_in of the snapped sigma through the denoiser's own module ON the device, as step_tab holds
+            tab[:, 2] = smp.denoiser.scaling(tab[:, 3])[2]  # it and the module route computes it (the host's may differ in the last bit)
+        smp.ge, smp.gc = smp.edm_tab[0].clone(), smp.corr_tab[0].clone()
+        smp.churned = bool((smp.churn_tab[:, 1] > 0).any())  # (once per schedule; a step reads nothing back)
+        smp.noise = None
+        if self.draws(smp):
+            smp.seed_buf = torch.tensor([S.seed_words(smp.seed)], dtype=torch.int64, device=dev)
+            smp.streams_buf = torch.zeros(x.shape[0], dtype=torch.int32, device=dev)
+            if smp.noise_streams is not None:
+                smp.set_noise_streams(smp.noise_streams)
+            smp.noise = S.DeviceNoise(smp.seed_buf, smp.streams_buf, smp.gi)
+
+    def build_stage(self, smp):  # the time-embedding rows of q(sigma_hat): the network is evaluated there, not at sigma_i
+        smp.edm_temb = smp.temb_rows(smp.edm_tab[:, 3])
+
+    def set_row(self, smp, i):  # (gi is the churn table's row and the noise counter's step word on this route as well)
+        smp.ge.copy_(smp.edm_tab[i])
+        smp.gc.copy_(smp.corr_tab[i])
+        smp.gi.copy_(smp._iota[i:i + 1])
+
+    def churn(self, smp):  # its own launch in front of stage-in, which reads a 3x3 halo of gx
+        if smp.churned:
+            ops.edm_churn(smp.gx, smp.churn_tab, smp.gi, smp.seed_buf, smp.streams_buf)
+
+    def staged_step(self, smp, evaluate):  # [churn] -> stage-in on edm_tab -> trunk -> [c_out at q(sigma_hat), CFG, to_d, Euler], in place
+        self.churn(smp)
+        eps_cl = evaluate(smp.gx, smp.edm_tab, smp.edm_temb)
+        return ops.cfg_edm_predict_cl(smp.gx, eps_cl, smp.edm_tab, smp.gi, smp.scale, smp.scale_im, smp.gx)
+
+    def step(self, smp, unet, x, s, s_next):  # the kernels on the rows in ge / gc and the step index in gi
+        return S.fused_cfg_edm_euler_step(smp.denoiser, unet, x, smp.ge, smp.churn_tab if smp.churned else None, smp.guider, noise=smp.noise)
+
+
+class Heun(ChurnedEuler):
+    """HeunEDMSampler (sampling.py:321-337: second order, TWO network evaluations per step, one on the sigma_next = 0 step; churn as for
+    Euler).  smp.gxe = the predictor's x_e and smp.gdir = its direction d, shaped like gx: both are written before they are read within a
+    step, so retarget() resets neither.  smp.last_row (set by the sampler: on the last step, and while it captures that step's graph)
+    is the reference's host-side skip of the corrector."""
+
+    single_last = True
+
+    def build(self, smp, x):
+        super().build(smp, x)
+        smp.gxe, smp.gdir = torch.zeros_like(x), torch.zeros_like(x)
+
+    def build_stage(self, smp):  # the corrector's evaluation: the network at q(sigma_next)
+        super().build_stage(smp)
+        smp.corr_temb = smp.temb_rows(smp.corr_tab[:, 3])
+
+    def staged_step(self, smp, evaluate):
+        if smp.last_row:
+            return super().staged_step(smp, evaluate)
+        self.churn(smp)
+        eps_cl = evaluate(smp.gx, smp.edm_tab, smp.edm_temb)
+        ops.cfg_edm_predict_cl(smp.gx, eps_cl, smp.edm_tab, smp.gi, smp.scale, smp.scale_im, smp.gxe, smp.gdir)
+        eps2_cl = evaluate(smp.gxe, smp.corr_tab, smp.corr_temb)  # h0 and emb_act are reused
+        return ops.cfg_edm_correct_cl(smp.gx, smp.gxe, smp.gdir, eps2_cl, smp.edm_tab, smp.corr_tab, smp.gi, smp.scale, smp.scale_im)
+
+    def step(self, smp, unet, x, s, s_next):
+        return S.fused_cfg_heun_step(smp.denoiser, unet, x, smp.ge, smp.gc, smp.churn_tab if smp.churned else None, smp.guider, noise=smp.noise,
+                                     last=smp.last_row)
+
+
+# the EDM family on include/cd360_edm.h: "heun", and the object solver="euler" runs on when s_churn > 0 (SOLVERS["euler"] stays the
+# un-churned one, kernels and launch count unchanged)
+EDM_SOLVERS = {"euler": ChurnedEuler(), "heun": Heun()}

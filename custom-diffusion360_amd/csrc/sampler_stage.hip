@@ -344,6 +344,126 @@ __global__ __launch_bounds__(256) void cfg_euler_ancestral_step_kernel(const flo
   }
 }
 
+// ---- the EDM family with churn, and Heun (sampling.py:85-136, 314-337: EDMSampler.sampler_step, HeunEDMSampler.possible_correction_step) ----
+// include/cd360_edm.h.  A churned step evaluates the network at sigma_hat = sigma (1 + gamma), which is not on the denoiser's grid:
+// DiscreteDenoiser snaps it, so c_out (and c_in, and the time-embedding row) come from sq = q(sigma_hat) while to_d and dt keep the
+// un-snapped sigma_hat.  edm [nsteps, 4] = (sigma_hat, sigma_next, c_in(sq), sq); corr [nsteps, 4] = the same for the corrector's evaluation
+// at sigma_next; churn [nsteps, 4] = (gamma, noise_std, s_noise, 0)  (cd360/sampler.py::edm_tables).
+
+// x [bs, 4, HW] fp32 IN PLACE: x <- x + (z * s_noise) * noise_std, z = sampler_noise4 of (pixel, step, the row's stream).  noise_std is one
+// table scalar, uniform over the launch: a noise_std == 0 row returns before x is touched.
+__global__ __launch_bounds__(256) void edm_churn_kernel(float* __restrict__ x, const float* __restrict__ churn, const int* __restrict__ step,
+                                                        const uint32_t* __restrict__ seed, const int* __restrict__ streams, int bs, long HW) {
+  const int idx = *step;
+  const float noise_std = churn[idx * 4 + 1], s_noise = churn[idx * 4 + 2];
+  if (noise_std == 0.f) return;
+  const uint32_t k0 = seed[0], k1 = seed[1];
+  const long total = (long)bs * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long smp = i / HW, px = i - smp * HW;
+    float z[4];
+    sampler_noise4((uint32_t)px, (uint32_t)idx, streams ? (uint32_t)streams[smp] : 0u, k0, k1, z);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const long at = (smp * 4 + c) * HW + px;
+      x[at] = x[at] + (z[c] * s_noise) * noise_std;
+    }
+  }
+}
+
+// the predictor: d = to_d(x, sigma_hat, d0), x_e = the Euler step to sigma_next (euler_update's expression, d kept)
+__device__ __forceinline__ float edm_predict(float xv, float d0, float sh, float sn, float& d) {
+  d = (xv - d0) / sh;
+  return xv + d * (sn - sh);
+}
+
+// the corrector: d_new = to_d(x_e, sigma_next, d0'), d' = (d + d_new) / 2, x' = x + d' dt
+__device__ __forceinline__ float edm_correct(float xv, float xev, float dv, float d0n, float sh, float sn) {
+  const float dnew = (xev - d0n) / sn;
+  const float dp = (dv + dnew) / 2.0f;
+  return xv + dp * (sn - sh);
+}
+
+// x, xe, dir [bs, 4, HW] fp32; xe == x is allowed (same index, elementwise), dir may be null; eps as for cfg_euler_step_cl_kernel
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_edm_predict_cl_kernel(const float* x, const uint16_t* __restrict__ eps, const float* __restrict__ tab,
+                                                                 const int* __restrict__ step, float scale, float scale_im, float* xe,
+                                                                 float* __restrict__ dir, int bs, long HW, int ld) {
+  const int idx = *step;
+  const float sh = tab[idx * 4], sn = tab[idx * 4 + 1], sq = tab[idx * 4 + 3];
+  const long total = (long)bs * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long smp = i / HW, px = i - smp * HW;
+    const EpsRow e = load_eps_row<NB>(eps, bs, HW, ld, smp, px);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const long at = (smp * 4 + c) * HW + px;
+      const float xv = x[at];
+      float d;
+      xe[at] = edm_predict(xv, cfg_combine_cl<NB>(e, c, xv, sq, scale, scale_im), sh, sn, d);
+      if (dir) dir[at] = d;
+    }
+  }
+}
+
+// the un-staged form: x [n] fp32, eps [NB n] fp32, row [4] = one row of edm -> xe [n], dir [n] or null
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_edm_predict_kernel(const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ row,
+                                                              float scale, float scale_im, float* __restrict__ xe, float* __restrict__ dir, long n) {
+  const float sh = row[0], sn = row[1], sq = row[3];
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float xv = x[i];
+    float d;
+    xe[i] = edm_predict(xv, cfg_combine_flat<NB>(eps, n, i, xv, sq, scale, scale_im), sh, sn, d);
+    if (dir) dir[i] = d;
+  }
+}
+
+// x [bs, 4, HW] fp32 IN PLACE (it holds x_hat); xe, dir read; eps2 = the network's output at (x_e, sigma_next).  sigma_next is one table
+// scalar, uniform over the launch: where it is not > 0 the row is x <- xe and neither eps2 nor dir is read (sampling.py:334-336)
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_edm_correct_cl_kernel(float* __restrict__ x, const float* __restrict__ xe, const float* __restrict__ dir,
+                                                                 const uint16_t* __restrict__ eps, const float* __restrict__ tab,
+                                                                 const float* __restrict__ corr, const int* __restrict__ step, float scale,
+                                                                 float scale_im, int bs, long HW, int ld) {
+  const int idx = *step;
+  const float sh = tab[idx * 4], sn = tab[idx * 4 + 1], sqn = corr[idx * 4 + 3];
+  const bool correct = sn > 0.f;
+  const long total = (long)bs * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long smp = i / HW, px = i - smp * HW;
+    if (!correct) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) x[(smp * 4 + c) * HW + px] = xe[(smp * 4 + c) * HW + px];
+      continue;
+    }
+    const EpsRow e = load_eps_row<NB>(eps, bs, HW, ld, smp, px);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const long at = (smp * 4 + c) * HW + px;
+      const float xev = xe[at];
+      x[at] = edm_correct(x[at], xev, dir[at], cfg_combine_cl<NB>(e, c, xev, sqn, scale, scale_im), sh, sn);
+    }
+  }
+}
+
+// the un-staged form: x, xe, dir [n] fp32, eps [NB n] fp32, row / crow [4] = one row of edm / corr -> out [n]
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_edm_correct_kernel(const float* __restrict__ x, const float* __restrict__ xe, const float* __restrict__ dir,
+                                                              const float* __restrict__ eps, const float* __restrict__ row,
+                                                              const float* __restrict__ crow, float scale, float scale_im, float* __restrict__ out,
+                                                              long n) {
+  const float sh = row[0], sn = row[1], sqn = crow[3];
+  const bool correct = sn > 0.f;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float xev = xe[i];
+    if (correct)
+      out[i] = edm_correct(x[i], xev, dir[i], cfg_combine_flat<NB>(eps, n, i, xev, sqn, scale, scale_im), sh, sn);
+    else
+      out[i] = xev;
+  }
+}
+
 // ---- host side of the tails ----
 inline unsigned tail_grid(long total) {  // grid-stride kernels: one thread per element up to 65536 workgroups
   const long blocks = (total + 255) / 256;
@@ -496,6 +616,84 @@ extern "C" int cd360_cfg_euler_ancestral_step_cl(void* x, const void* eps, const
     hipLaunchKernelGGL(cfg_euler_ancestral_step_cl_kernel<decltype(nb)::value>, dim3(tail_grid((long)bs * HW)), dim3(256), 0, (hipStream_t)stream,
                        (float*)x, (const uint16_t*)eps, (const float*)step_tab, (const float*)anc_tab, (const int*)step, (const uint32_t*)seed,
                        (const int*)streams, scale, sim, bs, (long)HW, ld);
+  });
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// include/cd360_edm.h.  x [bs, 4, HW] fp32 IN PLACE; churn_tab [nsteps, 4] fp32 = (gamma, noise_std, s_noise, 0); step: device int32, the row
+// of the table AND the noise counter's step word; seed / streams as for cd360_sampler_noise_f32 (noise_args_ok)
+extern "C" int cd360_edm_churn_f32(void* x, const void* churn_tab, const void* step, const void* seed, const void* streams, int bs, int64_t HW,
+                                   void* stream) {
+  if (!x || !churn_tab || bs <= 0 || HW <= 0 || !noise_args_ok(seed, streams, step, HW) || ((uintptr_t)x | (uintptr_t)churn_tab) % 4)
+    return CD360_ERR_ARG;
+  hipLaunchKernelGGL(edm_churn_kernel, dim3(tail_grid((long)bs * HW)), dim3(256), 0, (hipStream_t)stream, (float*)x, (const float*)churn_tab,
+                     (const int*)step, (const uint32_t*)seed, (const int*)streams, bs, (long)HW);
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// x, xe, dir [bs, 4, HW] fp32: xe == x (the in-place form) or a buffer of its own; dir null or a buffer of its own; eps, ld and the NaN
+// scale_im as for cd360_cfg_euler_step_cl; edm_tab [nsteps, 4] = (sigma_hat, sigma_next, c_in(sq), sq)
+extern "C" int cd360_cfg_edm_predict_cl(const void* x, const void* eps, const void* edm_tab, const void* step, float scale, float scale_im, void* xe,
+                                        void* dir, int bs, int64_t HW, int ld, void* stream) {
+  if (!cl_args_ok(x, eps, edm_tab, step, bs, HW, ld) || !xe || ((uintptr_t)x | (uintptr_t)xe | (uintptr_t)dir) % 4) return CD360_ERR_ARG;
+  const long bytes = (long)bs * 4 * HW * (long)sizeof(float);
+  if ((xe != x && overlap(xe, x, bytes)) || (dir && (overlap(dir, x, bytes) || overlap(dir, xe, bytes)))) return CD360_ERR_ARG;
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_edm_predict_cl_kernel<decltype(nb)::value>, dim3(tail_grid((long)bs * HW)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)x, (const uint16_t*)eps, (const float*)edm_tab, (const int*)step, scale, sim, (float*)xe, (float*)dir, bs,
+                       (long)HW, ld);
+  });
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// x [n] fp32, eps [3n] fp32 (u | ic | c) or, for a NaN scale_im, [2n] (u | c); row [4] = one row of edm_tab, a device tensor; xe [n] and
+// dir [n] (or null): buffers of their own (neither an input, nor each other)
+extern "C" int cd360_cfg_edm_predict_f32(const void* x, const void* eps, const void* row, float scale, float scale_im, void* xe, void* dir,
+                                         int64_t n, void* stream) {
+  if (!x || !eps || !row || !xe || n <= 0) return CD360_ERR_ARG;
+  const long bytes = (long)n * (long)sizeof(float), ebytes = bytes * (std::isnan(scale_im) ? 2 : 3);
+  if (overlap(xe, x, bytes) || overlap(xe, eps, bytes, ebytes)) return CD360_ERR_ARG;
+  if (dir && (overlap(dir, x, bytes) || overlap(dir, eps, bytes, ebytes) || overlap(dir, xe, bytes))) return CD360_ERR_ARG;
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_edm_predict_kernel<decltype(nb)::value>, dim3(tail_grid(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+                       (const float*)eps, (const float*)row, scale, sim, (float*)xe, (float*)dir, (long)n);
+  });
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// x [bs, 4, HW] fp32 IN PLACE; xe, dir [bs, 4, HW] fp32, read: three distinct buffers; eps2, ld and the NaN scale_im as for
+// cd360_cfg_euler_step_cl; edm_tab as above, corr_tab [nsteps, 4] = (sigma_next, sigma_next, c_in(sq'), sq') with sq' = q(sigma_next)
+extern "C" int cd360_cfg_edm_correct_cl(void* x, const void* xe, const void* dir, const void* eps2, const void* edm_tab, const void* corr_tab,
+                                        const void* step, float scale, float scale_im, int bs, int64_t HW, int ld, void* stream) {
+  if (!cl_args_ok(x, eps2, edm_tab, step, bs, HW, ld) || !xe || !dir || !corr_tab || ((uintptr_t)x | (uintptr_t)xe | (uintptr_t)dir) % 4)
+    return CD360_ERR_ARG;
+  const long bytes = (long)bs * 4 * HW * (long)sizeof(float);
+  if (overlap(x, xe, bytes) || overlap(x, dir, bytes) || overlap(xe, dir, bytes)) return CD360_ERR_ARG;
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_edm_correct_cl_kernel<decltype(nb)::value>, dim3(tail_grid((long)bs * HW)), dim3(256), 0, (hipStream_t)stream, (float*)x,
+                       (const float*)xe, (const float*)dir, (const uint16_t*)eps2, (const float*)edm_tab, (const float*)corr_tab, (const int*)step,
+                       scale, sim, bs, (long)HW, ld);
+  });
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// x, xe, dir [n] fp32, eps2 [3n] fp32 or, for a NaN scale_im, [2n]; row / corr_row [4] = one row of edm_tab / corr_tab, device tensors; out [n]: a
+// buffer of its own
+extern "C" int cd360_cfg_edm_correct_f32(const void* x, const void* xe, const void* dir, const void* eps2, const void* row, const void* corr_row,
+                                         float scale, float scale_im, void* out, int64_t n, void* stream) {
+  if (!x || !xe || !dir || !eps2 || !row || !corr_row || !out || n <= 0) return CD360_ERR_ARG;
+  const long bytes = (long)n * (long)sizeof(float);
+  if (overlap(out, x, bytes) || overlap(out, xe, bytes) || overlap(out, dir, bytes) || overlap(out, eps2, bytes, bytes * (std::isnan(scale_im) ? 2 : 3)))
+    return CD360_ERR_ARG;
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_edm_correct_kernel<decltype(nb)::value>, dim3(tail_grid(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+                       (const float*)xe, (const float*)dir, (const float*)eps2, (const float*)row, (const float*)corr_row, scale, sim, (float*)out,
+                       (long)n);
   });
   CD360_LAUNCH_CHECK();
   return CD360_OK;

@@ -1,17 +1,20 @@
 #!/usr/bin/env python
-"""Euler against DPM++ 2M and ancestral Euler through cd360.job.Sampler: the figures of DESIGN.md's sections on the further solvers.  Calls
-the job sampler directly (bench.py keeps measuring the Euler headline).
+"""Euler against DPM++ 2M, ancestral Euler, Heun and churned Euler through cd360.job.Sampler: the figures of DESIGN.md's sections on the
+further solvers.  Calls the job sampler directly (bench.py keeps measuring the Euler headline).
 
-  --solver euler|dpmpp2m|euler_a   which tail (euler also runs on a checkout that predates the `solver` argument: --repo PATH imports that
-                           checkout); euler_a: seed 360 on both routes
+  --solver euler|dpmpp2m|euler_a|heun   which step (euler also runs on a checkout that predates the `solver` argument: --repo PATH imports
+                           that checkout); euler_a and every churned run: seed 360 on both routes
+  --s-churn / --s-tmin / --s-tmax / --s-noise   the churn of EDMSampler's constructor, for --solver euler and heun (default: none)
   --branches 2|3           which guider
   --what deviation         n_steps = 4, all 4 steps at latent 32 / 6 views: the captured job sampler against the un-captured module route
-                           (cd360.sampler's EulerEDMSampler / DPMPP2MSampler / EulerAncestralSampler + the guider + DiscreteDenoiser around the same UNet, eager),
+                           (cd360.sampler's EulerEDMSampler / DPMPP2MSampler / EulerAncestralSampler / HeunEDMSampler + the guider + DiscreteDenoiser around the same UNet, eager),
                            max |difference| / max |module-route latent|: the yardstick and the figure of
                            tests/test_dpmpp2m_gpu.py::test_dpmpp2m_job_agrees_with_the_uncaptured_module_route and
-                           tests/test_euler_a_gpu.py::test_euler_a_job_agrees_with_the_uncaptured_module_route
+                           tests/test_euler_a_gpu.py::test_euler_a_job_agrees_with_the_uncaptured_module_route and
+                           tests/test_edm_gpu.py::test_edm_job_agrees_with_the_uncaptured_module_route
   --what timing            steady-step replay time of the graph sampler under Euler AND --solver in this process (median of --reps replays after
-                           warm-up, interleaved), at --latent / --refs (default 128 / 50)
+                           warm-up, interleaved), at --latent / --refs (default 128 / 50); a Heun steady step holds two
+                           evaluations (compare with two Euler steps), a churned Euler step one launch more than the plain one
 Prints one JSON line per figure."""
 import argparse
 import json
@@ -20,7 +23,11 @@ import statistics
 import sys
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--solver", default="dpmpp2m", choices=("euler", "dpmpp2m", "euler_a"))
+ap.add_argument("--solver", default="dpmpp2m", choices=("euler", "dpmpp2m", "euler_a", "heun"))
+ap.add_argument("--s-churn", type=float, default=0.0)
+ap.add_argument("--s-tmin", type=float, default=0.0)
+ap.add_argument("--s-tmax", type=float, default=float("inf"))
+ap.add_argument("--s-noise", type=float, default=1.0)
 ap.add_argument("--branches", type=int, default=3, choices=(2, 3))
 ap.add_argument("--what", default="deviation", choices=("deviation", "timing"))
 ap.add_argument("--repo", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -38,6 +45,10 @@ from cd360 import sampler as S  # noqa: E402
 DEV, BF, NB = "cuda", torch.bfloat16, args.branches
 SCALE_IM = 3.5 if NB == 3 else 0
 SEED = 360
+CHURN = dict(s_churn=args.s_churn, s_tmin=args.s_tmin, s_tmax=args.s_tmax, s_noise=args.s_noise) if args.s_churn > 0 else {}
+if CHURN and args.solver not in ("euler", "heun"):
+    ap.error("--s-churn applies to --solver euler and heun")
+LABEL = args.solver + ("_churn" if CHURN else "")
 
 
 def one_pose(p, latent, refs):
@@ -54,10 +65,11 @@ def batch(p, latent, refs):
     return [cam] * NB, torch.cat([c[0:1]] * (NB - 1) + [c[1:2]]), torch.cat([v[0:1]] * (NB - 1) + [v[1:2]]), x
 
 
-def make(net, pose, ctx, y, n_steps, solver):
+def make(net, pose, ctx, y, n_steps, solver, churn=None):
     kw = {} if solver == "euler" else {"solver": solver}  # (a checkout that predates the argument serves Euler)
-    if solver == "euler_a":
+    if solver == "euler_a" or churn:
         kw["seed"] = SEED
+    kw.update(churn or {})
     return job.Sampler(net, pose, ctx, y, n_steps, scale_im=SCALE_IM, use_graph=True, **kw)
 
 
@@ -70,12 +82,14 @@ def deviation():
     latent, refs, steps = 32, 6, 4
     net = bench.build_model(latent, refs, 50, DEV)
     pose, ctx, y, x0 = batch(0, latent, refs)
-    smp = make(net, pose, ctx, y, steps, args.solver)
+    smp = make(net, pose, ctx, y, steps, args.solver, CHURN)
     got = job.sample_assigned(smp, [(pose, ctx, y, x0)], steps)[0]
     gcfg = ({"target": "sgm.modules.diffusionmodules.guiders.VanillaCFGImgRef", "params": {"scale": 7.5}} if NB == 2 else
             {"target": "sgm.modules.diffusionmodules.guiders.ScheduledCFGImgTextRef", "params": {"scale": 7.5, "scale_im": 3.5}})
     if args.solver == "euler_a":
         mod = S.EulerAncestralSampler(num_steps=steps, guider_config=gcfg, device=DEV, seed=SEED)
+    elif args.solver == "heun" or CHURN:
+        mod = (S.HeunEDMSampler if args.solver == "heun" else S.EulerEDMSampler)(num_steps=steps, guider_config=gcfg, device=DEV, seed=SEED, **CHURN)
     else:
         mod = (S.EulerEDMSampler if args.solver == "euler" else S.DPMPP2MSampler)(num_steps=steps, guider_config=gcfg, device=DEV)
     den = S.DiscreteDenoiser().to(DEV)
@@ -88,14 +102,16 @@ def deviation():
     x, old = x0.clone(), None
     for i in range(steps):
         s, sn = sig[i].reshape(1), sig[i + 1].reshape(1)
-        if args.solver == "euler":
+        if args.solver == "heun" or CHURN:
+            x, _ = mod.sampler_step(s, sn, denoiser, x, c, uc, mod.gamma_of(sig[i], steps))
+        elif args.solver == "euler":
             x, _ = mod.sampler_step(s, sn, denoiser, x, c, uc)
         elif args.solver == "euler_a":
             x = mod.sampler_step(s, sn, denoiser, x, c, uc)
         else:
             x, old = mod.sampler_step(old, None if i == 0 else sig[i - 1].reshape(1), s, sn, denoiser, x, c, uc)
     sampling.clear_rendered_feat(net)
-    out(figure="job_vs_module_route", solver=args.solver, n_steps=steps, steps=steps, max_abs=float((got - x).abs().max()),
+    out(figure="job_vs_module_route", solver=LABEL, n_steps=steps, steps=steps, max_abs=float((got - x).abs().max()),
         rel=float((got - x).abs().max() / x.abs().max()), latent_max=float(x.abs().max()), staged=bool(smp.staged))
 
 
@@ -105,12 +121,12 @@ def timing():
     net = bench.build_model(latent, refs, 50, DEV)
     pose, ctx, y, x0 = batch(0, latent, refs)
     smps = {}
-    for solver in ("euler", "dpmpp2m" if args.solver == "euler" else args.solver):
-        smp = make(net, pose, ctx, y, 50, solver)
+    for label, solver, churn in (("euler", "euler", None), ("dpmpp2m", "dpmpp2m", None) if LABEL == "euler" else (LABEL, args.solver, CHURN)):
+        smp = make(net, pose, ctx, y, 50, solver, churn)
         x = smp.step(x0.clone(), 0, alias=True)
         for i in range(1, 4):
             x = smp.step(x, i, alias=True)
-        smps[solver] = smp
+        smps[label] = smp
     torch.cuda.synchronize()
 
     def timed(smp, i):
