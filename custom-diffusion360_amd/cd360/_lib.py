@@ -1,5 +1,5 @@
-"""ctypes binding of libcd360_hip.so (the C ABI declared in include/cd360_hip.h, include/cd360_solvers.h and
-include/cd360_stochastic.h).
+"""ctypes binding of libcd360_hip.so (the C ABI declared in include/cd360_hip.h, include/cd360_solvers.h,
+include/cd360_stochastic.h, include/cd360_edm.h and include/cd360_highorder.h).
 
 There is NO fallback: if the shared library is missing or a symbol is absent this module raises.
 The library is built in-tree by `__graft_entry__.build()` (hipcc --offload-arch=gfx950)."""
@@ -136,6 +136,17 @@ EDM_SIGNATURES = {
     "cd360_cfg_edm_correct_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_float, _P, c_int64, _P]),
 }
 
+# include/cd360_highorder.h: the tails of DPM++ 2S ancestral (midpoint, step) and of the linear multistep solver.  A fifth table, bound and
+# symbol-checked like the others.
+HIGHORDER_SIGNATURES = {
+    "cd360_cfg_dpmpp2s_mid_cl": (c_int, [_P, _P, _P, _P, _P, c_float, c_float, _P, c_int, c_int64, c_int, _P]),
+    "cd360_cfg_dpmpp2s_mid_f32": (c_int, [_P, _P, _P, _P, c_float, c_float, _P, c_int64, _P]),
+    "cd360_cfg_dpmpp2s_step_cl": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_int, c_int64, c_int, _P]),
+    "cd360_cfg_dpmpp2s_step_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_float, c_float, _P, c_int, c_int64, _P]),
+    "cd360_cfg_lms_step_cl": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_float, c_int, c_int, c_int64, c_int, _P]),
+    "cd360_cfg_lms_step_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_float, c_int, _P, c_int64, _P]),
+}
+
 TUNING_FIELDS = ("gemm_cfg", "gemm_group_m", "gemm_movers", "gemm_ksplit", "conv_cfg", "conv_dma", "conv_kgroup", "conv_wide", "conv_wmajor",
                  "conv_split", "attn_smallk", "attn_smallk_wgs", "attn_self", "attn_fast", "nerf_kernel", "qattn_cfg", "whatif", "gemm_small", "qattn_keys16",
                  "qattn_split", "store_wt", "conv_halo", "gemm_asm4")
@@ -181,7 +192,8 @@ def load(check_symbols: bool = True):
     lib = ctypes.CDLL(LIB_PATH)
     if os.environ.get("CD360_LIB"):
         check_symbols = False  # an explicitly named older / probe build (same-box A/B): entry points it predates stay unbound
-    for name, (res, args) in (*SIGNATURES.items(), *SOLVER_SIGNATURES.items(), *STOCHASTIC_SIGNATURES.items(), *EDM_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *SOLVER_SIGNATURES.items(), *STOCHASTIC_SIGNATURES.items(), *EDM_SIGNATURES.items(),
+                              *HIGHORDER_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -37,23 +37,34 @@ class Sampler:
     snapped sigma_hat, the Euler step from sigma_hat -- and `seed` / `noise_streams` / `reseed` / `set_noise_streams` apply to it; with
     s_churn = 0 it is the step it has always been.  "heun" (HeunEDMSampler, sampling.py:321-337, churn as for Euler) evaluates the UNet
     twice per step inside ONE captured graph and once on the sigma_next = 0 step, which has a graph of its own; `self.gxe` / `self.gdir`
-    hold the predictor's latent and direction between the two evaluations."""
+    hold the predictor's latent and direction between the two evaluations.
+    "dpmpp2s_a" (DPMPP2SAncestralSampler, sampling.py:350-387; `eta` / `s_noise` / `seed` / `noise_streams` as for "euler_a") evaluates the
+    UNet at (x, sigma) and at the midpoint (`self.gx2`, sigma_mid snapped to the denoiser's grid) inside ONE captured graph
+    (include/cd360_highorder.h); the rows with sigma_down = 0 -- the last, and for eta > 1 interior rows (`self.single_rows`) -- are the
+    ancestral Euler step with one evaluation, on the one-evaluation graph.  "lms" (LinearMultistepSampler, sampling.py:276-311, `order` in
+    1..4) keeps the last `order` directions in the ring `self.gds`; like DPM++ 2M's `gd` it is not reset between images, so `step(x, i)` for
+    i > 0 must follow `step(., i - 1)` of the SAME image."""
 
     SOLVERS = tuple(solvers.SOLVERS)
     EDM_SOLVERS = tuple(k for k in solvers.EDM_SOLVERS if k not in solvers.SOLVERS)  # the names only the EDM registry serves
+    HIGHORDER_SOLVERS = tuple(solvers.HIGHORDER_SOLVERS)
 
     def __init__(self, net, pose, ctx, y, n_steps, scale=7.5, scale_im=3.5, use_graph=False, prefetch=None, graph_render=True, solver="euler",
-                 eta=1.0, s_noise=1.0, seed=0, noise_streams=None, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf")):
+                 eta=1.0, s_noise=1.0, seed=0, noise_streams=None, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), order=4):
         from cd360 import sampler as S
-        if solver not in self.SOLVERS + self.EDM_SOLVERS:
-            raise ValueError(f"solver {solver!r}: the job sampler serves {', '.join(self.SOLVERS + self.EDM_SOLVERS)}")
+        names = self.SOLVERS + self.EDM_SOLVERS + self.HIGHORDER_SOLVERS
+        if solver not in names:
+            raise ValueError(f"solver {solver!r}: the job sampler serves {', '.join(names)}")
+        if solver == "lms" and (isinstance(order, bool) or not isinstance(order, int) or not 1 <= order <= 4):
+            raise ValueError(f"order {order!r}: the linear multistep solver serves orders 1..4")
         # the name, and what only that solver knows (cd360/solvers.py): the EDM registry serves its own names, and every name it shares with
         # the first one as soon as the schedule churns
         edm = solver in solvers.EDM_SOLVERS and (solver not in solvers.SOLVERS or s_churn > 0)
-        self.solver, self._solver = solver, (solvers.EDM_SOLVERS if edm else solvers.SOLVERS)[solver]
+        registry = solvers.HIGHORDER_SOLVERS if solver in solvers.HIGHORDER_SOLVERS else solvers.EDM_SOLVERS if edm else solvers.SOLVERS
+        self.solver, self._solver, self.order = solver, registry[solver], order
         self.eta, self.s_noise, self.seed, self.noise_streams = eta, s_noise, seed, noise_streams
         self.s_churn, self.s_tmin, self.s_tmax = s_churn, s_tmin, s_tmax
-        self.last_row = False  # True while the step at hand is the sigma_next = 0 step of a solver that shapes it differently (single_last)
+        self.last_row = False  # True while the step at hand is a one-evaluation row of a two-evaluation solver (Solver.single_row)
         self.net, self.pose, self.n_steps = net, pose, n_steps
         if use_graph:  # the graphs read the cameras through ONE buffer this sampler owns (retarget rewrites it in place)
             from sgm.modules.utils_cameraray import PoseBuffer
@@ -281,8 +292,9 @@ class Sampler:
     @torch.no_grad()
     def prepare(self, x):
         """Untimed set-up of the graph mode: one eager render (builds the per-image tables and the static cache buffers), then the
-        steady-state step and the render step are each captured once -- and, for a solver whose sigma_next = 0 step has another shape
-        (Heun: one evaluation instead of two), that step a third time.  All graphs read / write the same static buffers."""
+        steady-state step and the render step are each captured once -- and, for a solver some of whose rows have another shape (Heun's
+        sigma_next = 0 step, DPM++ 2S's sigma_down = 0 rows: one evaluation instead of two), that shape a third time.  All graphs read /
+        write the same static buffers."""
         if not self.use_graph or self._prepared:
             return
         self._prepared = True
@@ -291,19 +303,20 @@ class Sampler:
             self._build_stage(x)
         else:
             self._build_state(x)
-        if self._solver.single_last and self.n_steps == 1:
-            return  # the only step renders AND is the sigma_next = 0 row: launched un-captured
+        single = [self._solver.single_row(self, i) for i in range(self.n_steps)]
+        if single[0] and self.n_steps == 1:
+            return  # the only step renders AND is a one-evaluation row: launched un-captured
         self._render()
         if self.staged:
             self.gx.copy_(x)  # (the staged step updates gx in place: captures and warm-ups below start from a sane latent again)
         self.graph, self.gout = self._capture(self._math_static)
-        if self._solver.single_last:
+        if any(single):
             self.last_row = True
             try:
                 self.lgraph, self.lout = self._capture(self._math_static)
             finally:
                 self.last_row = False
-        if self.graph_render:
+        if self.graph_render and not single[0]:  # (a one-evaluation row 0 renders un-captured)
             try:
                 self.rgraph, self.rout = self._capture(self._render)
                 self._pins = self._snapshot_pins()
@@ -353,7 +366,7 @@ class Sampler:
         if (self.staged or self.use_graph) and x is not self.gx:  # these steps run on the sampler's own latent buffer
             self.gx.copy_(x)
         self._set_step(i)
-        self.last_row = last = self._solver.single_last and i == self.n_steps - 1
+        self.last_row = last = self._solver.single_row(self, i)
         if not self.use_graph:
             if i == 0:
                 from cd360 import sampling

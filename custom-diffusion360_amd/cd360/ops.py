@@ -1439,6 +1439,114 @@ def cfg_edm_correct_cl(x: torch.Tensor, xe: torch.Tensor, d: torch.Tensor, eps2_
     return x
 
 
+def _like(x: torch.Tensor, *ts: torch.Tensor):
+    for t in ts:
+        assert t.dtype == torch.float32 and t.shape == x.shape and t.is_contiguous()
+
+
+def _tab_like(ref: torch.Tensor, *tabs: torch.Tensor):
+    for t in tabs:
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == ref.shape
+
+
+def cfg_dpmpp2s_mid(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, mult: torch.Tensor, scale: float, scale_im: Optional[float]):
+    """The midpoint tail of a DPM++ 2S step (cd360_cfg_dpmpp2s_mid_f32, include/cd360_highorder.h): x [n,...] fp32, eps [3n,...] fp32 (u | ic |
+    c) or, with scale_im=None, [2n,...] (u | c), sigma a 1-element and mult = (m1, m2, m3, m4) a 4-element fp32 device tensor -> x2 = m1 x -
+    m2 d0, a new tensor."""
+    _need_gpu(x, eps, sigma, mult)
+    sim = _cfg_flat_args(x, eps, scale_im)
+    assert sigma.dtype == torch.float32 and sigma.numel() == 1
+    _edm_row(mult)
+    x2 = torch.empty_like(x)
+    check(_lib.load().cd360_cfg_dpmpp2s_mid_f32(_ptr(x), _ptr(eps), _ptr(sigma), _ptr(mult), float(scale), sim, _ptr(x2), x.numel(), _stream()),
+          "cd360_cfg_dpmpp2s_mid_f32")
+    return x2
+
+
+def cfg_dpmpp2s_mid_cl(x: torch.Tensor, eps_cl: torch.Tensor, step_tab: torch.Tensor, mult2s_tab: torch.Tensor, step: torch.Tensor, scale: float,
+                       scale_im: Optional[float], x2: torch.Tensor):
+    """Midpoint tail of a captured DPM++ 2S step (cd360_cfg_dpmpp2s_mid_cl): x [bs, 4, H, W] fp32 READ, eps_cl as for cfg_euler_step_cl, sigma =
+    step_tab[step][0], (m1, m2) = mult2s_tab[step][0 / 1]; x2 (a buffer of its own) is written."""
+    _need_gpu(x, eps_cl, step_tab, mult2s_tab, step, x2)
+    bs, hw, ld, sim = _cfg_cl_args(x, eps_cl, step_tab, step, scale_im)
+    _like(x, x2)
+    _tab_like(step_tab, mult2s_tab)
+    check(_lib.load().cd360_cfg_dpmpp2s_mid_cl(_ptr(x), _ptr(eps_cl), _ptr(step_tab), _ptr(mult2s_tab), _ptr(step), float(scale), sim, _ptr(x2), bs,
+                                              hw, ld, _stream()), "cd360_cfg_dpmpp2s_mid_cl")
+    return x2
+
+
+def cfg_dpmpp2s_step(x: torch.Tensor, x2: torch.Tensor, eps2: torch.Tensor, mid_row: torch.Tensor, mult: torch.Tensor, anc: torch.Tensor,
+                     seed: torch.Tensor, streams: Optional[torch.Tensor], step: torch.Tensor, scale: float, scale_im: Optional[float]):
+    """The second tail of a DPM++ 2S step (cd360_cfg_dpmpp2s_step_f32): x, x2 [bs, 4, H, W] fp32, eps2 = the network at (x2, sigma_mid) [3 bs,
+    ...] or [2 bs, ...] fp32, mid_row / mult / anc = one row of mid_tab / mult2s_tab / anc_tab -> x' = m3 x - m4 d0' (d0' combined from x2 at
+    sq_mid), plus (z s_noise) sigma_up where sigma_up != 0, z = sampler_noise(seed, streams, step, ...) drawn inside the kernel; a new tensor."""
+    _need_gpu(x, x2, eps2, mid_row, mult, anc, seed, streams, step)
+    sim = _cfg_flat_args(x, eps2, scale_im)
+    assert x.ndim == 4 and x.shape[1] == 4
+    _like(x, x2)
+    for row in (mid_row, mult, anc):
+        _edm_row(row)
+    bs = x.shape[0]
+    _noise_args(seed, streams, step, bs)
+    out = torch.empty_like(x)
+    check(_lib.load().cd360_cfg_dpmpp2s_step_f32(_ptr(x), _ptr(x2), _ptr(eps2), _ptr(mid_row), _ptr(mult), _ptr(anc), _ptr(seed), _ptr(streams),
+                                                _ptr(step), float(scale), sim, _ptr(out), bs, x.shape[2] * x.shape[3], _stream()),
+          "cd360_cfg_dpmpp2s_step_f32")
+    return out
+
+
+def cfg_dpmpp2s_step_cl(x: torch.Tensor, x2: torch.Tensor, eps2_cl: torch.Tensor, mid_tab: torch.Tensor, mult2s_tab: torch.Tensor,
+                        anc_tab: torch.Tensor, step: torch.Tensor, seed: torch.Tensor, streams: Optional[torch.Tensor], scale: float,
+                        scale_im: Optional[float]):
+    """Second tail of a captured DPM++ 2S step, IN PLACE on x [bs, 4, H, W] fp32 (cd360_cfg_dpmpp2s_step_cl): x2 read, eps2_cl as for
+    cfg_euler_step_cl, sq_mid = mid_tab[step][3], (m3, m4) = mult2s_tab[step][2 / 3], (sigma_up, s_noise) = anc_tab[step][1 / 2]; the noise is
+    drawn inside the kernel (none when sigma_up == 0)."""
+    _need_gpu(x, x2, eps2_cl, mid_tab, mult2s_tab, anc_tab, step, seed, streams)
+    bs, hw, ld, sim = _cfg_cl_args(x, eps2_cl, mid_tab, step, scale_im)
+    _like(x, x2)
+    _tab_like(mid_tab, mult2s_tab, anc_tab)
+    _noise_args(seed, streams, step, bs)
+    check(_lib.load().cd360_cfg_dpmpp2s_step_cl(_ptr(x), _ptr(x2), _ptr(eps2_cl), _ptr(mid_tab), _ptr(mult2s_tab), _ptr(anc_tab), _ptr(step),
+                                               _ptr(seed), _ptr(streams), float(scale), sim, bs, hw, ld, _stream()), "cd360_cfg_dpmpp2s_step_cl")
+    return x
+
+
+def _lms_ring(x: torch.Tensor, ring: torch.Tensor) -> int:
+    assert ring.dtype == torch.float32 and ring.is_contiguous() and ring.ndim == x.ndim + 1 and tuple(ring.shape[1:]) == tuple(x.shape)
+    return ring.shape[0]
+
+
+def cfg_lms_step(x: torch.Tensor, eps: torch.Tensor, ring: torch.Tensor, sigma: torch.Tensor, row: torch.Tensor, step: torch.Tensor, scale: float,
+                 scale_im: Optional[float]):
+    """One linear multistep tail (cd360_cfg_lms_step_f32, include/cd360_highorder.h): x [n,...] fp32, eps [3n,...] or [2n,...] fp32, ring
+    [order, n,...] fp32 (order 1..4), sigma a 1-element and row = (c_0 .. c_3) a 4-element fp32 device tensor, step a device int32 = the
+    index i of the step -> x' = x + sum_j c_j d_(i - j), a new tensor; d_i = (x - d0) / sigma is stored into ring[i % order], and only the
+    min(i + 1, order) - 1 slots before it are read."""
+    _need_gpu(x, eps, ring, sigma, row, step)
+    sim = _cfg_flat_args(x, eps, scale_im)
+    order = _lms_ring(x, ring)
+    assert sigma.dtype == torch.float32 and sigma.numel() == 1 and step.dtype == torch.int32 and step.numel() == 1
+    _edm_row(row)
+    out = torch.empty_like(x)
+    check(_lib.load().cd360_cfg_lms_step_f32(_ptr(x), _ptr(eps), _ptr(ring), _ptr(sigma), _ptr(row), _ptr(step), float(scale), sim, order, _ptr(out),
+                                            x.numel(), _stream()), "cd360_cfg_lms_step_f32")
+    return out
+
+
+def cfg_lms_step_cl(x: torch.Tensor, ring: torch.Tensor, eps_cl: torch.Tensor, step_tab: torch.Tensor, lms_tab: torch.Tensor, step: torch.Tensor,
+                    scale: float, scale_im: Optional[float]):
+    """Linear multistep tail of a captured sampling step, IN PLACE on x [bs, 4, H, W] fp32 and on ring [order, bs, 4, H, W] fp32
+    (cd360_cfg_lms_step_cl): eps_cl as for cfg_euler_step_cl, sigma = step_tab[step][0], (c_0 .. c_3) = lms_tab[step]."""
+    _need_gpu(x, ring, eps_cl, step_tab, lms_tab, step)
+    bs, hw, ld, sim = _cfg_cl_args(x, eps_cl, step_tab, step, scale_im)
+    order = _lms_ring(x, ring)
+    _tab_like(step_tab, lms_tab)
+    check(_lib.load().cd360_cfg_lms_step_cl(_ptr(x), _ptr(ring), _ptr(eps_cl), _ptr(step_tab), _ptr(lms_tab), _ptr(step), float(scale), sim, order,
+                                           bs, hw, ld, _stream()), "cd360_cfg_lms_step_cl")
+    return x
+
+
 def out_conv4_ok(H: int, W: int, cin: int) -> bool:
     return W in (32, 64, 128) and H % 2 == 0 and cin % 64 == 0 and H * W * cin * 2 < 2 ** 31
 

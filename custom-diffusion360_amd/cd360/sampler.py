@@ -7,7 +7,7 @@ custom-diffusion360_amd/sgm/modules/diffusionmodules/), so the YAML sampler/deno
 
 Everything stays on the device and nothing synchronises: the sigma -> index quantisation is an argmin + gather on the GPU, and
 with `fused=True` the per-step tail (c_out scaling, 3-way or 2-way CFG combine, to_d, Euler update) is one HIP kernel
-(cd360_cfg_euler_step_f32) instead of ~10 tiny elementwise launches.  DPMPP2MSampler, EulerAncestralSampler and the EDM tables are at the end.
+(cd360_cfg_euler_step_f32) instead of ~10 tiny elementwise launches.  The further samplers and their tables are at the end.
 """
 from __future__ import annotations
 
@@ -532,7 +532,7 @@ class EulerAncestralSampler(BaseDiffusionSampler):
     def _seeded_noise(self, x):
         if not x.is_cuda:
             from ._lib import Cd360Error
-            raise Cd360Error("the seeded noise of EulerAncestralSampler is drawn by a HIP kernel; got a CPU tensor (seed=None draws torch.randn_like)")
+            raise Cd360Error(f"the seeded noise of {type(self).__name__} is drawn by a HIP kernel; got a CPU tensor (seed=None draws torch.randn_like)")
         if self._noise is None or self._noise.seed.device != x.device:
             self._noise = DeviceNoise(torch.tensor([seed_words(self.seed)], dtype=torch.int64, device=x.device), None,
                                       torch.zeros(1, dtype=torch.int32, device=x.device))
@@ -739,3 +739,257 @@ def fused_cfg_heun_step(denoiser: "DiscreteDenoiser", network: Callable, x: torc
         return xe
     eps2 = cfg_eps(denoiser, network, xe, corr_row.reshape(4)[0], guider.branches)
     return cfg_edm_correct(x_hat, xe, d, eps2.contiguous(), edm_row, corr_row, scale, scale_im, fused=fused)
+
+
+# ----------------------------------------------------------------------------------------------- DPM++ 2S ancestral
+class DPMPP2SAncestralSampler(EulerAncestralSampler):
+    """DPM-Solver++(2S) with ancestral noise (sampling.py:350-387): the step to sigma_down is taken through a SECOND network evaluation at
+    (x2, to_sigma(s)), s the midpoint of sigma and sigma_down in -log sigma -- x2 = m1 x - m2 denoised, x' = m3 x - m4 denoised2 --, then the
+    ancestral noise s_noise sigma_up is added where sigma_next > 0.  Where sigma_down = 0 (the last step; for eta > 1 interior steps as well)
+    the step is the ancestral Euler step and costs one evaluation: n steps cost 2n - (such steps) evaluations.  to_sigma(s) is off the
+    denoiser's grid; it goes to the denoiser un-snapped and the denoiser snaps it.  Constructor, `noise_sampler` and `seed` as in
+    EulerAncestralSampler: seed=None draws torch.randn_like; seed=<int> the library's generator with step word = the number of draws since
+    __call__ began -- one per step, the last included, as the reference's torch.where evaluates its noisy branch everywhere.
+
+    The reference's class does not run in its own fork as written, for the reasons EulerAncestralSampler's docstring names: `denoise` returns
+    (denoised, rgb_list) and sampler_step uses that tuple as a tensor, __call__ returns x alone, and eta = 0 hands the Python float 0.0 to
+    append_dims.  Here `denoise` is unpacked -- the arithmetic is the reference's, operation by operation, get_variables / get_mult included
+    --, the rgb_list of the last denoise call is kept on the instance, __call__ returns (x, rgb_list), and eta = 0 is served as the
+    deterministic DPM++ 2S (sigma_down = sigma_next, nothing drawn)."""
+
+    def get_variables(self, sigma, sigma_down):
+        t, t_next = [to_neg_log_sigma(s) for s in (sigma, sigma_down)]
+        h = t_next - t
+        s = t + 0.5 * h
+        return h, s, t, t_next
+
+    def get_mult(self, h, s, t, t_next):
+        mult1 = to_sigma(s) / to_sigma(t)
+        mult2 = (-0.5 * h).expm1()
+        mult3 = to_sigma(t_next) / to_sigma(t)
+        mult4 = (-h).expm1()
+        return mult1, mult2, mult3, mult4
+
+    def sampler_step(self, sigma, next_sigma, denoiser, x, cond, uc=None, **kwargs):
+        sigma_down, sigma_up = get_ancestral_step(sigma, next_sigma, eta=self.eta)
+        denoised, self.rgb_list = self.denoise(x, denoiser, sigma, cond, uc)
+        x_euler = self.ancestral_euler_step(x, denoised, sigma, sigma_down)
+        if torch.sum(sigma_down) < 1e-14:  # save a network evaluation if all noise levels are 0
+            x = x_euler
+        else:
+            h, s, t, t_next = self.get_variables(sigma, sigma_down)
+            mult = [append_dims(m, x.ndim) for m in self.get_mult(h, s, t, t_next)]
+            x2 = mult[0] * x - mult[1] * denoised
+            denoised2, self.rgb_list = self.denoise(x2, denoiser, to_sigma(s), cond, uc)
+            x_dpmpp2s = mult[2] * x - mult[3] * denoised2
+            x = torch.where(append_dims(sigma_down, x.ndim) > 0.0, x_dpmpp2s, x_euler)  # apply correction if noise level is not 0
+        return self.ancestral_step(x, sigma, next_sigma, sigma_up)
+
+
+def dpmpp2s_tables(sigmas: torch.Tensor, denoiser: "DiscreteDenoiser", eta: float = 1.0, s_noise: float = 1.0):
+    """The per-schedule tables of DPMPP2SAncestralSampler (include/cd360_highorder.h): sigmas [n + 1] (the discretisation's output, last = 0)
+    -> three [n, 4] fp32 tables, row i in the reference's own expressions and order (sampling.py:351-363, sampling_utils.py:27-36):
+
+        anc_tab     (sigma_down, sigma_up, s_noise, 0)                  euler_ancestral_table as it is
+        mid_tab     (sigma_mid, sigma_down, c_in(sq_mid), sq_mid)       sigma_mid = to_sigma(s), s = t + 0.5 h; sq_mid =
+                                                                        denoiser.possibly_quantize_sigma(sigma_mid): the second evaluation's
+                                                                        c_in / c_out / time-embedding row (edm_tables' corr_tab layout)
+        mult2s_tab  (mult1, mult2, mult3, mult4)                        get_mult(*get_variables(sigma, sigma_down))
+
+    A row with sigma_down < 1e-14 takes ONE evaluation (sampling.py:370-372: the ancestral Euler step) and reads neither mid_tab nor mult2s_tab;
+    it holds finite filler -- mid = the step's own (sigma, sigma_next, c_in, sigma), mults = 0 -- so a capture warm-up on it stays finite.
+    Computed in CPU fp32 whatever device `sigmas` and the denoiser live on, and uploaded by the caller: graph, eager and fresh samplers share its
+    bits."""
+    sig = sigmas.detach().to("cpu", torch.float32)
+    grid = denoiser.sigmas.detach().to("cpu", torch.float32)
+    anc = euler_ancestral_table(sig, eta, s_noise)
+    one = DPMPP2SAncestralSampler.__new__(DPMPP2SAncestralSampler)
+
+    def snapped(s):  # DiscreteDenoiser.possibly_quantize_sigma + the scaling's c_in, on the host
+        sq = grid[(s - grid[:, None]).abs().argmin(dim=0).view(s.shape)]
+        return denoiser.scaling(sq)[2], sq
+
+    mid, mult = [], []
+    for i in range(sig.numel() - 1):
+        s, sn, sd = sig[i].reshape(1), sig[i + 1].reshape(1), anc[i, 0].reshape(1)
+        if float(sd) < 1e-14:
+            c_in, sq = snapped(s)
+            mid.append(torch.cat([s, sn, c_in, sq]))
+            mult.append(torch.zeros(4))
+            continue
+        h, sm, t, t_next = one.get_variables(s, sd)
+        s_mid = to_sigma(sm)
+        c_in, sq = snapped(s_mid)
+        mid.append(torch.cat([s_mid, sd, c_in, sq]))
+        mult.append(torch.cat(list(one.get_mult(h, sm, t, t_next))))
+    return anc, torch.stack(mid).contiguous(), torch.stack(mult).contiguous()
+
+
+def dpmpp2s_single_rows(anc_tab: torch.Tensor):
+    """The rows of a DPM++ 2S schedule that take one evaluation (sigma_down < 1e-14: sampling.py:370), as a host list of bools."""
+    return [float(v) < 1e-14 for v in anc_tab.detach().to("cpu")[:, 0]]
+
+
+def cfg_dpmpp2s_mid(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, mult: torch.Tensor, scale: float, scale_im: Optional[float] = None,
+                    fused: bool = True) -> torch.Tensor:
+    """The midpoint tail of a CFG DPM++ 2S step with EpsScaling -> x2 = m1 x - m2 d0: den_b = x - sigma eps_b, d0 = the guider's combine as in
+    cfg_euler_update, (m1, m2, ., .) = mult, one row of dpmpp2s_tables' third table (cd360_cfg_dpmpp2s_mid_f32).  fused=False: the same chain
+    in plain torch, in the kernel's order."""
+    cfg_branch_count(x, eps, scale_im)
+    if fused and x.is_cuda:
+        from . import ops
+        return ops.cfg_dpmpp2s_mid(x, eps, sigma, mult.reshape(4), scale, scale_im)
+    m1, m2 = mult.reshape(4)[0], mult.reshape(4)[1]
+    return m1 * x - m2 * cfg_combine(x, eps, sigma, scale, scale_im)
+
+
+def cfg_dpmpp2s_update(x: torch.Tensor, x2: torch.Tensor, eps2: torch.Tensor, mid_row: torch.Tensor, mult: torch.Tensor, anc_row: torch.Tensor,
+                       scale: float, scale_im: Optional[float] = None, noise=None, fused: bool = True) -> torch.Tensor:
+    """The second tail of a CFG DPM++ 2S step -> x': den_b = x2 - sq_mid eps2_b, d0' = the guider's combine, x_n = m3 x - m4 d0', x' = x_n if
+    sigma_up == 0 else x_n + (z * s_noise) * sigma_up; x = the latent the midpoint read, x2 its output, eps2 = the network at (x2, sigma_mid),
+    sq_mid = column 3 of mid_row, (., ., m3, m4) = mult, (., sigma_up, s_noise, .) = anc_row (cd360_cfg_dpmpp2s_step_f32).  `noise` as
+    cfg_euler_ancestral_update takes it: a DeviceNoise -- fused: ONE kernel that draws z itself -- or a tensor z shaped like x, added by torch
+    in the kernel's order behind the kernel's sigma_up = 0 form.  fused=False: the same chain in plain torch, in the kernel's order."""
+    cfg_branch_count(x, eps2, scale_im)
+    if fused and x.is_cuda and isinstance(noise, DeviceNoise):  # (nothing read back: this is the call a captured un-staged step makes)
+        from . import ops
+        return ops.cfg_dpmpp2s_step(x, x2, eps2, mid_row.reshape(4), mult.reshape(4), anc_row.reshape(4), noise.seed, noise.streams, noise.step,
+                                    scale, scale_im)
+    sd, su, s_noise, _ = anc_row.reshape(4).unbind()
+    noisy = float(su) != 0.0
+    if noisy and noise is None:
+        raise ValueError("sigma_up != 0: the step needs `noise` (a DeviceNoise or a tensor shaped like x)")
+    if fused and x.is_cuda:
+        from . import ops
+        dry = DeviceNoise(torch.zeros(1, dtype=torch.int64, device=x.device), None, torch.zeros(1, dtype=torch.int32, device=x.device))
+        x_n = ops.cfg_dpmpp2s_step(x, x2, eps2, mid_row.reshape(4), mult.reshape(4), torch.stack([sd, torch.zeros_like(su), s_noise, torch.zeros_like(su)]),
+                                   dry.seed, None, dry.step, scale, scale_im)
+        return x_n + (noise * s_noise) * su if noisy else x_n
+    m3, m4 = mult.reshape(4)[2], mult.reshape(4)[3]
+    x_n = m3 * x - m4 * cfg_combine(x2, eps2, mid_row.reshape(4)[3], scale, scale_im)
+    if not noisy:
+        return x_n
+    z = noise.draw(x) if isinstance(noise, DeviceNoise) else noise
+    return x_n + (z * s_noise) * su
+
+
+def fused_cfg_dpmpp2s_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, sigma: torch.Tensor, anc_row: torch.Tensor,
+                           mid_row: torch.Tensor, mult: torch.Tensor, guider, noise=None, fused: bool = True, single: Optional[bool] = None):
+    """ONE step of DPMPP2SAncestralSampler.sampler_step (sampling.py:365-387) in the form the sampling job launches it:
+
+        eps  = network(c_in(sigma) [x] * B, idx(sigma))              the first evaluation, on the grid
+        x2   = cfg_dpmpp2s_mid(x, eps, sigma, mult)                  cd360_cfg_dpmpp2s_mid_f32
+        eps2 = network(c_in(sq_mid) [x2] * B, idx(sq_mid))           DiscreteDenoiser.network_inputs snaps sigma_mid ON the device
+        x'   = cfg_dpmpp2s_update(x, x2, eps2, mid_row, mult, anc_row, noise)        cd360_cfg_dpmpp2s_step_f32
+
+    `anc_row` / `mid_row` / `mult` = row i of dpmpp2s_tables(...) for sigma = sigmas[i]; `noise` as cfg_dpmpp2s_update takes it.  `single`:
+    the row takes one evaluation (sigma_down < 1e-14) and is fused_cfg_euler_ancestral_step; None reads it from anc_row (one read-back: a
+    captured step passes the flag)."""
+    if single is None:
+        single = float(anc_row.reshape(4)[0]) < 1e-14
+    if single:
+        return fused_cfg_euler_ancestral_step(denoiser, network, x, sigma, anc_row, guider, noise=noise, fused=fused)
+    scale, scale_im = guider_scales(guider)
+    eps = cfg_eps(denoiser, network, x, sigma, guider.branches)
+    x2 = cfg_dpmpp2s_mid(x, eps.contiguous(), sigma.reshape(1), mult, scale, scale_im, fused=fused)
+    eps2 = cfg_eps(denoiser, network, x2, mid_row.reshape(4)[0], guider.branches)
+    return cfg_dpmpp2s_update(x, x2, eps2.contiguous(), mid_row, mult, anc_row, scale, scale_im, noise=noise, fused=fused)
+
+
+# ----------------------------------------------------------------------------------------------- linear multistep
+def lms_coefficients(sigmas: torch.Tensor, order: int = 4) -> torch.Tensor:
+    """The per-schedule table of LinearMultistepSampler: sigmas [n + 1] (the discretisation's output) -> [n, 4] fp32, row i =
+    linear_multistep_coeff(min(i + 1, order), sigmas, i, j) for j < min(i + 1, order) (sampling_utils.py:12-24), zero behind them; order in
+    1..4.  The reference integrates the Lagrange basis polynomial over [sigma_i, sigma_(i+1)] with scipy's adaptive quadrature; its degree
+    is at most 3, so the 4-point Gauss-Legendre rule used here (float64, on the fp32 sigmas) is exact and scipy is not needed.
+    Computed on the host whatever device `sigmas` lives on, and uploaded by the caller: graph, eager and fresh samplers share its bits."""
+    if isinstance(order, bool) or not isinstance(order, int) or not 1 <= order <= 4:
+        raise ValueError(f"order {order!r}: the linear multistep solver serves orders 1..4")
+    t = sigmas.detach().to("cpu", torch.float32).numpy().astype(np.float64)
+    nodes, weights = np.polynomial.legendre.leggauss(4)
+    out = np.zeros((t.size - 1, 4), dtype=np.float32)
+    for i in range(t.size - 1):
+        cur = min(i + 1, order)
+        half, centre = 0.5 * (t[i + 1] - t[i]), 0.5 * (t[i + 1] + t[i])
+        tau = half * nodes + centre
+        for j in range(cur):
+            prod = np.ones_like(tau)
+            for k in range(cur):
+                if j != k:
+                    prod = prod * ((tau - t[i - k]) / (t[i - j] - t[i - k]))
+            out[i, j] = half * float(np.dot(weights, prod))
+    return torch.from_numpy(out).contiguous()
+
+
+class LinearMultistepSampler(BaseDiffusionSampler):
+    """Adams-Bashforth over the sigma schedule (sampling.py:276-311): x' = x + sum_j c_j d_(i - j) over the last min(i + 1, order) directions
+    d = to_d(x, sigma, denoised), c_j the integral of the j-th Lagrange basis polynomial of their sigmas over [sigma_i, sigma_(i+1)].  One
+    network evaluation per step, deterministic.  `ds` holds at most `order` directions, the coefficients multiply them newest first, and the
+    sum is formed in the reference's order (Python's sum) before it is added to x.
+
+    The reference's class does not run in its own fork as written: it unpacks two values from a denoiser that returns four, and __call__
+    returns x alone where DiffusionEngine.sample unpacks two values.  Here the denoiser's four values are unpacked -- the arithmetic is the
+    reference's, operation by operation --, the rgb_list of the last denoiser call is kept on the instance, and __call__ returns (x,
+    rgb_list).  The coefficients come from lms_coefficients (no scipy; exact for these polynomials) and are rounded to fp32 before they
+    multiply an fp32 direction, which is what torch does with the reference's Python floats."""
+
+    def __init__(self, order=4, discretization_config=None, num_steps: Optional[int] = None, guider_config=None, verbose: bool = False,
+                 device: str = "cuda"):
+        super().__init__(discretization_config, num_steps, guider_config, verbose, device)
+        self.order = order
+        self.rgb_list = None
+
+    def sampler_step(self, ds, coeffs, sigma, denoiser, x, cond, uc=None, **kwargs):
+        """One pass of the reference's loop body: `ds` = the list of kept directions (appended to and trimmed IN PLACE), `coeffs` = the step's
+        min(i + 1, order) coefficients, newest first."""
+        denoised, _, _, self.rgb_list = denoiser(*self.guider.prepare_inputs(x, sigma, cond, uc), **kwargs)
+        denoised = self.guider(denoised, sigma)
+        d = (x - denoised) / append_dims(sigma, x.ndim)
+        ds.append(d)
+        if len(ds) > self.order:
+            ds.pop(0)
+        return x + sum(coeff * d for coeff, d in zip(coeffs, reversed(ds)))
+
+    def __call__(self, denoiser: Callable, x, cond: Dict, uc=None, num_steps=None, **kwargs):
+        x, s_in, sigmas, num_sigmas, cond, uc = self.prepare_sampling_loop(x, cond, uc, num_steps)
+        ds = []
+        table = lms_coefficients(sigmas, self.order)
+        for i in range(num_sigmas - 1):
+            cur_order = min(i + 1, self.order)
+            x = self.sampler_step(ds, [float(table[i, j]) for j in range(cur_order)], s_in * sigmas[i], denoiser, x, cond, uc, **kwargs)
+        return x, self.rgb_list
+
+    forward = __call__
+
+
+def cfg_lms_update(x: torch.Tensor, eps: torch.Tensor, ring: torch.Tensor, sigma: torch.Tensor, coef: torch.Tensor, step, scale: float,
+                   scale_im: Optional[float] = None, fused: bool = True) -> torch.Tensor:
+    """One fused tail of a CFG linear multistep step with EpsScaling -> x': den_b = x - sigma eps_b, d0 = the guider's combine as in
+    cfg_euler_update, d = (x - d0) / sigma stored into ring[i % order] IN PLACE, acc = c_0 d, acc += c_j ring[(i - j) % order] for j = 1 ..
+    min(i + 1, order) - 1, x' = x + acc; ring [order, *x.shape] fp32, coef = one row of lms_coefficients, i = `step` (an int, or -- fused: the
+    device int32 the kernel reads, nothing read back -- a tensor).  Slots with j >= min(i + 1, order) are not read (cd360_cfg_lms_step_f32).
+    fused=False: the same chain in plain torch, in the kernel's order."""
+    cfg_branch_count(x, eps, scale_im)
+    if fused and x.is_cuda:
+        from . import ops
+        if not isinstance(step, torch.Tensor):
+            step = torch.tensor([int(step)], dtype=torch.int32, device=x.device)
+        return ops.cfg_lms_step(x, eps, ring, sigma, coef.reshape(4), step, scale, scale_im)
+    i, order = int(step), ring.shape[0]
+    d = (x - cfg_combine(x, eps, sigma, scale, scale_im)) / sigma
+    ring[i % order] = d
+    c = coef.reshape(4)
+    acc = c[0] * d
+    for j in range(1, min(i + 1, order)):
+        acc = acc + c[j] * ring[(i - j) % order]
+    return x + acc
+
+
+def fused_cfg_lms_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, ring: torch.Tensor, sigma: torch.Tensor, coef: torch.Tensor,
+                       step, guider, fused: bool = True) -> torch.Tensor:
+    """ONE pass of LinearMultistepSampler's loop (sampling.py:294-309) in the form the sampling job launches it: fused_cfg_euler_step with the
+    tail replaced -- x' = cfg_lms_update(x, eps, ring, sigma, coef, step): cd360_cfg_lms_step_f32.  `coef` = row i of
+    lms_coefficients(sigmas, order) for sigma = sigmas[i], `step` = i; `ring` carries the directions between the steps of ONE image."""
+    scale, scale_im = guider_scales(guider)
+    eps = cfg_eps(denoiser, network, x, sigma, guider.branches)
+    return cfg_lms_update(x, eps.contiguous(), ring, sigma.reshape(1), coef, step, scale, scale_im, fused=fused)

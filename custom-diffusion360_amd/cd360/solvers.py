@@ -3,7 +3,8 @@ un-staged route, the tail kernel that ends a staged step, its un-staged step, an
 solver; the state lives on the Sampler `smp` they are handed (smp.mult_tab, smp.gd, smp.anc_tab, smp.seed_buf, smp.streams_buf, smp.edm_tab,
 smp.corr_tab, smp.churn_tab, smp.gxe, smp.gdir: the names tests and tools read), next to the buffers every solver shares (smp.gx, smp.gi,
 smp._iota, smp.step_tab).  SOLVERS holds the one-evaluation solvers on the step table; EDM_SOLVERS the EDM family on its own tables
-(include/cd360_edm.h): Heun, and the Euler step of a schedule that churns."""
+(include/cd360_edm.h): Heun, and the Euler step of a schedule that churns; HIGHORDER_SOLVERS DPM++ 2S ancestral and the linear multistep
+solver (include/cd360_highorder.h; smp.mid_tab, smp.mult2s_tab, smp.gx2, smp.single_rows; smp.lms_tab, smp.gds)."""
 from __future__ import annotations
 
 import torch
@@ -18,6 +19,11 @@ class Solver:
 
     draws_noise = False
     single_last = False  # True: the sigma_next = 0 step differs in SHAPE from the others (fewer evaluations) and is captured on its own
+
+    def single_row(self, smp, i) -> bool:
+        """Does step i take ONE network evaluation where the solver's other steps take two?  Such rows run on a graph of their own
+        (smp.lgraph) with smp.last_row set.  The default is Heun's answer: the last row only, for a solver that says single_last."""
+        return self.single_last and i == smp.n_steps - 1
 
     def draws(self, smp) -> bool:
         return self.draws_noise
@@ -186,3 +192,74 @@ class Heun(ChurnedEuler):
 # the EDM family on include/cd360_edm.h: "heun", and the object solver="euler" runs on when s_churn > 0 (SOLVERS["euler"] stays the
 # un-churned one, kernels and launch count unchanged)
 EDM_SOLVERS = {"euler": ChurnedEuler(), "heun": Heun()}
+
+
+class DPMPP2SAncestral(EulerAncestral):
+    """DPMPP2SAncestralSampler (sampling.py:350-387: second order, single step, TWO network evaluations per step -- the second at the
+    midpoint sigma_mid, off the denoiser's grid -- and the ancestral noise of EulerAncestralSampler; smp.eta / smp.s_noise as the reference's
+    constructor takes them).  A row with sigma_down = 0 (the last; for eta > 1 interior rows as well: smp.single_rows) takes one evaluation
+    and is exactly the ancestral Euler step: it runs the parent's tail, on the one-evaluation graph.  smp.gx2 = the midpoint latent,
+    written before it is read within a step, so retarget() does not reset it."""
+
+    def build(self, smp, x):
+        """EulerAncestral's table and generator buffers, then the two further tables of cd360.sampler.dpmpp2s_tables (host fp32, uploaded;
+        c_in of the second evaluation re-derived on the device from the uploaded snapped sigma, as the step table's is), the host list of
+        the one-evaluation rows, the un-staged step's row buffers and gx2."""
+        super().build(smp, x)
+        anc, mid, mult = S.dpmpp2s_tables(smp.sigmas, smp.denoiser, smp.eta, smp.s_noise)  # (anc: the table super().build uploaded)
+        smp.single_rows = S.dpmpp2s_single_rows(anc)
+        smp.mid_tab, smp.mult2s_tab = mid.to(x.device), mult.to(x.device)
+        smp.mid_tab[:, 2] = smp.denoiser.scaling(smp.mid_tab[:, 3])[2]
+        smp.gmid, smp.gm2s = smp.mid_tab[0].clone(), smp.mult2s_tab[0].clone()
+        smp.gx2 = torch.zeros_like(x)
+
+    def single_row(self, smp, i) -> bool:
+        return smp.single_rows[i]
+
+    def build_stage(self, smp):  # the second evaluation: the network at q(sigma_mid)
+        smp.mid_temb = smp.temb_rows(smp.mid_tab[:, 3])
+
+    def set_row(self, smp, i):
+        super().set_row(smp, i)
+        smp.gmid.copy_(smp.mid_tab[i])
+        smp.gm2s.copy_(smp.mult2s_tab[i])
+
+    def staged_step(self, smp, evaluate):
+        if smp.last_row:  # one evaluation -> the ancestral Euler tail
+            return super().staged_step(smp, evaluate)
+        eps_cl = evaluate(smp.gx, smp.step_tab, smp.temb_tab)
+        ops.cfg_dpmpp2s_mid_cl(smp.gx, eps_cl, smp.step_tab, smp.mult2s_tab, smp.gi, smp.scale, smp.scale_im, smp.gx2)
+        eps2_cl = evaluate(smp.gx2, smp.mid_tab, smp.mid_temb)  # h0 and emb_act are reused
+        return ops.cfg_dpmpp2s_step_cl(smp.gx, smp.gx2, eps2_cl, smp.mid_tab, smp.mult2s_tab, smp.anc_tab, smp.gi, smp.seed_buf, smp.streams_buf,
+                                       smp.scale, smp.scale_im)
+
+    def step(self, smp, unet, x, s, s_next):  # the kernels on the rows in ga / gmid / gm2s and the step index in gi
+        return S.fused_cfg_dpmpp2s_step(smp.denoiser, unet, x, s, smp.ga, smp.gmid, smp.gm2s, smp.guider, noise=smp.noise, single=smp.last_row)
+
+
+class LMS(Solver):
+    """LinearMultistepSampler (sampling.py:276-311: Adams-Bashforth of order smp.order <= 4 over the sigma schedule, one UNet evaluation per
+    step, deterministic)."""
+
+    def build(self, smp, x):
+        """The coefficient table (host, uploaded: the same bits in every sampler of a schedule), the un-staged step's 4-float row buffer,
+        and gds = the ring of the last `order` directions, [order, *x.shape], shared by both captured graphs.  retarget() does not reset
+        it: step i reads only the min(i + 1, order) - 1 slots written by the steps before it, so row 0 reads no old slot -- which is also
+        why step(x, i) for i > 0 must follow step(., i - 1) of the same image."""
+        smp.lms_tab = S.lms_coefficients(smp.sigmas, smp.order).to(x.device)
+        smp.gl = smp.lms_tab[0].clone()
+        smp.gds = torch.zeros((smp.order,) + tuple(x.shape), dtype=x.dtype, device=x.device)
+
+    def set_row(self, smp, i):  # (gi names the ring slot on this route as well)
+        smp.gl.copy_(smp.lms_tab[i])
+        smp.gi.copy_(smp._iota[i:i + 1])
+
+    def tail(self, smp, eps_cl):  # x and the ring in place: [c_out, CFG, to_d, multistep sum]
+        return ops.cfg_lms_step_cl(smp.gx, smp.gds, eps_cl, smp.step_tab, smp.lms_tab, smp.gi, smp.scale, smp.scale_im)
+
+    def step(self, smp, unet, x, s, s_next):  # the kernel on the row in gl and the step index in gi
+        return S.fused_cfg_lms_step(smp.denoiser, unet, x, smp.gds, s, smp.gl, smp.gi, smp.guider)
+
+
+# the solvers on include/cd360_highorder.h
+HIGHORDER_SOLVERS = {"dpmpp2s_a": DPMPP2SAncestral(), "lms": LMS()}

@@ -464,6 +464,156 @@ __global__ __launch_bounds__(256) void cfg_edm_correct_kernel(const float* __res
   }
 }
 
+// ---- DPM++ 2S ancestral and linear multistep (sampling.py:350-387, 276-311) -------------------------------------------------------------
+// include/cd360_highorder.h.  DPM++ 2S evaluates the network twice per step: at (x, sigma) and at (x2, to_sigma(s)), the midpoint in
+// -log sigma between sigma and sigma_down, which is NOT on the denoiser's grid: c_out of the second evaluation is sq_mid = q(sigma_mid).
+// mid [nsteps, 4] = (sigma_mid, sigma_down, c_in(sq_mid), sq_mid); m2s [nsteps, 4] = (m1, m2, m3, m4) of get_mult; anc as above
+// (cd360/sampler.py::dpmpp2s_tables).  Rows with sigma_down = 0 run the ancestral Euler tail above instead (one evaluation).
+__device__ __forceinline__ float dpmpp2s_mix(float xv, float d0, float ma, float mb) { return ma * xv - mb * d0; }
+
+// x [bs, 4, HW] fp32 READ; x2 [bs, 4, HW] fp32 written; eps as for cfg_euler_step_cl_kernel; tab [nsteps, 4] (column 0 = sigma)
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_dpmpp2s_mid_cl_kernel(const float* __restrict__ x, const uint16_t* __restrict__ eps,
+                                                                 const float* __restrict__ tab, const float* __restrict__ m2s,
+                                                                 const int* __restrict__ step, float scale, float scale_im, float* __restrict__ x2,
+                                                                 int bs, long HW, int ld) {
+  const int idx = *step;
+  const float s = tab[idx * 4], m1 = m2s[idx * 4], m2 = m2s[idx * 4 + 1];
+  const long total = (long)bs * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long smp = i / HW, px = i - smp * HW;
+    const EpsRow e = load_eps_row<NB>(eps, bs, HW, ld, smp, px);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const long at = (smp * 4 + c) * HW + px;
+      const float xv = x[at];
+      x2[at] = dpmpp2s_mix(xv, cfg_combine_cl<NB>(e, c, xv, s, scale, scale_im), m1, m2);
+    }
+  }
+}
+
+// the un-staged form: x [n] fp32, eps [NB n] fp32, sigma [1], mult [4] = one row of m2s -> x2 [n]
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_dpmpp2s_mid_kernel(const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ sigma,
+                                                              const float* __restrict__ mult, float scale, float scale_im, float* __restrict__ x2,
+                                                              long n) {
+  const float s = *sigma, m1 = mult[0], m2 = mult[1];
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float xv = x[i];
+    x2[i] = dpmpp2s_mix(xv, cfg_combine_flat<NB>(eps, n, i, xv, s, scale, scale_im), m1, m2);
+  }
+}
+
+// x' = m3 x - m4 d0', d0' combined from x2 at sq_mid; then the ancestral noise where sigma_up != 0 (euler_ancestral_update's last line)
+__device__ __forceinline__ float dpmpp2s_update(float xv, float d0n, float m3, float m4, float su, float s_noise, float z, bool noisy) {
+  const float xn = dpmpp2s_mix(xv, d0n, m3, m4);
+  return noisy ? xn + (z * s_noise) * su : xn;
+}
+
+// x [bs, 4, HW] fp32 IN PLACE; x2 read; eps = the network's output at (x2, sigma_mid)
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_dpmpp2s_step_cl_kernel(float* __restrict__ x, const float* __restrict__ x2, const uint16_t* __restrict__ eps,
+                                                                  const float* __restrict__ mid, const float* __restrict__ m2s,
+                                                                  const float* __restrict__ anc, const int* __restrict__ step,
+                                                                  const uint32_t* __restrict__ seed, const int* __restrict__ streams, float scale,
+                                                                  float scale_im, int bs, long HW, int ld) {
+  const int idx = *step;
+  const float sqm = mid[idx * 4 + 3], m3 = m2s[idx * 4 + 2], m4 = m2s[idx * 4 + 3];
+  const float su = anc[idx * 4 + 1], s_noise = anc[idx * 4 + 2];
+  const bool noisy = su != 0.f;
+  const uint32_t k0 = seed[0], k1 = seed[1];
+  const long total = (long)bs * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long smp = i / HW, px = i - smp * HW;
+    const EpsRow e = load_eps_row<NB>(eps, bs, HW, ld, smp, px);
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (noisy) sampler_noise4((uint32_t)px, (uint32_t)idx, streams ? (uint32_t)streams[smp] : 0u, k0, k1, z);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const long at = (smp * 4 + c) * HW + px;
+      x[at] = dpmpp2s_update(x[at], cfg_combine_cl<NB>(e, c, x2[at], sqm, scale, scale_im), m3, m4, su, s_noise, z[c], noisy);
+    }
+  }
+}
+
+// the un-staged form: x, x2 [bs, 4, HW] fp32, eps [NB bs, 4, HW] fp32, midrow / mult / ancrow [4] = one row of mid / m2s / anc -> out
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_dpmpp2s_step_kernel(const float* __restrict__ x, const float* __restrict__ x2, const float* __restrict__ eps,
+                                                               const float* __restrict__ midrow, const float* __restrict__ mult,
+                                                               const float* __restrict__ ancrow, const uint32_t* __restrict__ seed,
+                                                               const int* __restrict__ streams, const int* __restrict__ step, float scale,
+                                                               float scale_im, float* __restrict__ out, int bs, long HW) {
+  const float sqm = midrow[3], m3 = mult[2], m4 = mult[3];
+  const float su = ancrow[1], s_noise = ancrow[2];
+  const bool noisy = su != 0.f;
+  const uint32_t k0 = seed[0], k1 = seed[1], st = (uint32_t)*step;
+  const long total = (long)bs * HW, n = total * 4;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long smp = i / HW, px = i - smp * HW;
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (noisy) sampler_noise4((uint32_t)px, st, streams ? (uint32_t)streams[smp] : 0u, k0, k1, z);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const long at = (smp * 4 + c) * HW + px;
+      out[at] = dpmpp2s_update(x[at], cfg_combine_flat<NB>(eps, n, at, x2[at], sqm, scale, scale_im), m3, m4, su, s_noise, z[c], noisy);
+    }
+  }
+}
+
+// Linear multistep: d = to_d(x, sigma, d0) goes into slot step % order of a ring of the last `order` directions; x' = x + sum_j c_j d_(step - j)
+// over j < min(step + 1, order), newest first, the sum formed before it is added (sampling.py:300-309).  coef = (c_0 .. c_3) of the step,
+// zero-padded (cd360/sampler.py::lms_coefficients).  Slots with j >= min(step + 1, order) are NOT read: on the first steps of an image they
+// hold the previous image's directions or uninitialised memory, and 0 * NaN must not reach x.  Element `at` of every slot belongs to the
+// thread that owns element `at` of x: no thread reads what another writes.
+__device__ __forceinline__ float lms_update(float xv, float d0, float s, const float coef[4], float* __restrict__ ring, long slot_elems, long at,
+                                            int idx, int order) {
+  const float d = (xv - d0) / s;
+  ring[(long)(idx % order) * slot_elems + at] = d;
+  const int cur = idx + 1 < order ? idx + 1 : order;
+  float acc = coef[0] * d;
+  for (int j = 1; j < cur; ++j) acc += coef[j] * ring[(long)((idx - j) % order) * slot_elems + at];
+  return xv + acc;
+}
+
+// x [bs, 4, HW] fp32 IN PLACE; ring [order, bs, 4, HW] fp32; eps as for cfg_euler_step_cl_kernel; tab [nsteps, 4] (column 0 = sigma);
+// lms [nsteps, 4]
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_lms_step_cl_kernel(float* __restrict__ x, float* __restrict__ ring, const uint16_t* __restrict__ eps,
+                                                              const float* __restrict__ tab, const float* __restrict__ lms,
+                                                              const int* __restrict__ step, float scale, float scale_im, int order, int bs, long HW,
+                                                              int ld) {
+  const int idx = *step;
+  const float s = tab[idx * 4];
+  const float coef[4] = {lms[idx * 4], lms[idx * 4 + 1], lms[idx * 4 + 2], lms[idx * 4 + 3]};
+  const long total = (long)bs * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long smp = i / HW, px = i - smp * HW;
+    const EpsRow e = load_eps_row<NB>(eps, bs, HW, ld, smp, px);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const long at = (smp * 4 + c) * HW + px;
+      const float xv = x[at];
+      x[at] = lms_update(xv, cfg_combine_cl<NB>(e, c, xv, s, scale, scale_im), s, coef, ring, total * 4, at, idx, order);
+    }
+  }
+}
+
+// the un-staged form: x [n] fp32, eps [NB n] fp32, ring [order, n] fp32 (slot step % order written), sigma [1], row [4] = one row of lms,
+// step: device int32 -> out [n]
+template <int NB>
+__global__ __launch_bounds__(256) void cfg_lms_step_kernel(const float* __restrict__ x, const float* __restrict__ eps, float* __restrict__ ring,
+                                                           const float* __restrict__ sigma, const float* __restrict__ row,
+                                                           const int* __restrict__ step, float scale, float scale_im, int order,
+                                                           float* __restrict__ out, long n) {
+  const int idx = *step;
+  const float s = *sigma;
+  const float coef[4] = {row[0], row[1], row[2], row[3]};
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float xv = x[i];
+    out[i] = lms_update(xv, cfg_combine_flat<NB>(eps, n, i, xv, s, scale, scale_im), s, coef, ring, n, i, idx, order);
+  }
+}
+
 // ---- host side of the tails ----
 inline unsigned tail_grid(long total) {  // grid-stride kernels: one thread per element up to 65536 workgroups
   const long blocks = (total + 255) / 256;
@@ -693,6 +843,107 @@ extern "C" int cd360_cfg_edm_correct_f32(const void* x, const void* xe, const vo
   launch_for_branches(scale_im, [&](auto nb, float sim) {
     hipLaunchKernelGGL(cfg_edm_correct_kernel<decltype(nb)::value>, dim3(tail_grid(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
                        (const float*)xe, (const float*)dir, (const float*)eps2, (const float*)row, (const float*)corr_row, scale, sim, (float*)out,
+                       (long)n);
+  });
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// include/cd360_highorder.h.  x [bs, 4, HW] fp32, read; x2 [bs, 4, HW] fp32: a buffer of its own; eps, ld and the NaN scale_im as for
+// cd360_cfg_euler_step_cl; step_tab [nsteps, 4] (sigma = column 0), mult2s_tab [nsteps, 4] = (m1, m2, m3, m4)
+extern "C" int cd360_cfg_dpmpp2s_mid_cl(const void* x, const void* eps, const void* step_tab, const void* mult2s_tab, const void* step, float scale,
+                                        float scale_im, void* x2, int bs, int64_t HW, int ld, void* stream) {
+  if (!cl_args_ok(x, eps, step_tab, step, bs, HW, ld) || !mult2s_tab || !x2 || ((uintptr_t)x | (uintptr_t)x2) % 4) return CD360_ERR_ARG;
+  if (overlap(x, x2, (long)bs * 4 * HW * (long)sizeof(float))) return CD360_ERR_ARG;
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_dpmpp2s_mid_cl_kernel<decltype(nb)::value>, dim3(tail_grid((long)bs * HW)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)x, (const uint16_t*)eps, (const float*)step_tab, (const float*)mult2s_tab, (const int*)step, scale, sim,
+                       (float*)x2, bs, (long)HW, ld);
+  });
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// x [n] fp32, eps [3n] fp32 (u | ic | c) or, for a NaN scale_im, [2n] (u | c); sigma [1], mult [4] = one row of mult2s_tab, device tensors; x2 [n]:
+// a buffer of its own
+extern "C" int cd360_cfg_dpmpp2s_mid_f32(const void* x, const void* eps, const void* sigma, const void* mult, float scale, float scale_im, void* x2,
+                                         int64_t n, void* stream) {
+  if (!x || !eps || !sigma || !mult || !x2 || n <= 0) return CD360_ERR_ARG;
+  const long bytes = (long)n * (long)sizeof(float);
+  if (overlap(x2, x, bytes) || overlap(x2, eps, bytes, bytes * (std::isnan(scale_im) ? 2 : 3))) return CD360_ERR_ARG;
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_dpmpp2s_mid_kernel<decltype(nb)::value>, dim3(tail_grid(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+                       (const float*)eps, (const float*)sigma, (const float*)mult, scale, sim, (float*)x2, (long)n);
+  });
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// x [bs, 4, HW] fp32 IN PLACE; x2 [bs, 4, HW] fp32, read: distinct buffers; eps2, ld and the NaN scale_im as for cd360_cfg_euler_step_cl;
+// mid_tab [nsteps, 4] = (sigma_mid, sigma_down, c_in(sq_mid), sq_mid), mult2s_tab as above, anc_tab [nsteps, 4] = (sigma_down, sigma_up,
+// s_noise, 0); step = the row of the three tables AND the noise counter's step word
+extern "C" int cd360_cfg_dpmpp2s_step_cl(void* x, const void* x2, const void* eps2, const void* mid_tab, const void* mult2s_tab, const void* anc_tab,
+                                         const void* step, const void* seed, const void* streams, float scale, float scale_im, int bs, int64_t HW,
+                                         int ld, void* stream) {
+  if (!cl_args_ok(x, eps2, mid_tab, step, bs, HW, ld) || !x2 || !mult2s_tab || !anc_tab || !noise_args_ok(seed, streams, step, HW) ||
+      ((uintptr_t)x | (uintptr_t)x2) % 4)
+    return CD360_ERR_ARG;
+  if (overlap(x, x2, (long)bs * 4 * HW * (long)sizeof(float))) return CD360_ERR_ARG;
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_dpmpp2s_step_cl_kernel<decltype(nb)::value>, dim3(tail_grid((long)bs * HW)), dim3(256), 0, (hipStream_t)stream, (float*)x,
+                       (const float*)x2, (const uint16_t*)eps2, (const float*)mid_tab, (const float*)mult2s_tab, (const float*)anc_tab,
+                       (const int*)step, (const uint32_t*)seed, (const int*)streams, scale, sim, bs, (long)HW, ld);
+  });
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// x, x2 [bs, 4, HW] fp32, eps2 [3 bs, 4, HW] fp32 or, for a NaN scale_im, [2 bs, 4, HW]; mid_row / mult / anc [4] = one row of mid_tab /
+// mult2s_tab / anc_tab, device tensors; out [bs, 4, HW]: a buffer of its own
+extern "C" int cd360_cfg_dpmpp2s_step_f32(const void* x, const void* x2, const void* eps2, const void* mid_row, const void* mult, const void* anc,
+                                          const void* seed, const void* streams, const void* step, float scale, float scale_im, void* out, int bs,
+                                          int64_t HW, void* stream) {
+  if (!x || !x2 || !eps2 || !mid_row || !mult || !anc || !out || bs <= 0 || HW <= 0 || !noise_args_ok(seed, streams, step, HW)) return CD360_ERR_ARG;
+  const long bytes = (long)bs * 4 * HW * (long)sizeof(float);
+  if (overlap(out, x, bytes) || overlap(out, x2, bytes) || overlap(out, eps2, bytes, bytes * (std::isnan(scale_im) ? 2 : 3))) return CD360_ERR_ARG;
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_dpmpp2s_step_kernel<decltype(nb)::value>, dim3(tail_grid((long)bs * HW)), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)x, (const float*)x2, (const float*)eps2, (const float*)mid_row, (const float*)mult, (const float*)anc,
+                       (const uint32_t*)seed, (const int*)streams, (const int*)step, scale, sim, (float*)out, bs, (long)HW);
+  });
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// x [bs, 4, HW] fp32 IN PLACE; ring [order, bs, 4, HW] fp32: slot step % order written, the min(step + 1, order) - 1 slots before it read; eps,
+// ld and the NaN scale_im as for cd360_cfg_euler_step_cl; step_tab [nsteps, 4] (sigma = column 0), lms_tab [nsteps, 4] = (c_0 .. c_3); order 1..4
+extern "C" int cd360_cfg_lms_step_cl(void* x, void* ring, const void* eps, const void* step_tab, const void* lms_tab, const void* step, float scale,
+                                     float scale_im, int order, int bs, int64_t HW, int ld, void* stream) {
+  if (!cl_args_ok(x, eps, step_tab, step, bs, HW, ld) || !ring || !lms_tab || order < 1 || order > 4 || ((uintptr_t)x | (uintptr_t)ring) % 4)
+    return CD360_ERR_ARG;
+  const long bytes = (long)bs * 4 * HW * (long)sizeof(float);
+  if (overlap(x, ring, bytes, bytes * order)) return CD360_ERR_ARG;
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_lms_step_cl_kernel<decltype(nb)::value>, dim3(tail_grid((long)bs * HW)), dim3(256), 0, (hipStream_t)stream, (float*)x,
+                       (float*)ring, (const uint16_t*)eps, (const float*)step_tab, (const float*)lms_tab, (const int*)step, scale, sim, order, bs,
+                       (long)HW, ld);
+  });
+  CD360_LAUNCH_CHECK();
+  return CD360_OK;
+}
+
+// x [n] fp32, eps [3n] fp32 or, for a NaN scale_im, [2n]; ring [order, n] fp32, slot step % order written; sigma [1], row [4] = one row of
+// lms_tab, step [1] int32: device tensors; out [n]: a buffer of its own (neither an input nor the ring)
+extern "C" int cd360_cfg_lms_step_f32(const void* x, const void* eps, void* ring, const void* sigma, const void* row, const void* step, float scale,
+                                      float scale_im, int order, void* out, int64_t n, void* stream) {
+  if (!x || !eps || !ring || !sigma || !row || !step || !out || n <= 0 || order < 1 || order > 4) return CD360_ERR_ARG;
+  const long bytes = (long)n * (long)sizeof(float), ebytes = bytes * (std::isnan(scale_im) ? 2 : 3);
+  if (overlap(out, x, bytes) || overlap(out, eps, bytes, ebytes) || overlap(out, ring, bytes, bytes * order) || overlap(ring, x, bytes * order, bytes) ||
+      overlap(ring, eps, bytes * order, ebytes))
+    return CD360_ERR_ARG;
+  launch_for_branches(scale_im, [&](auto nb, float sim) {
+    hipLaunchKernelGGL(cfg_lms_step_kernel<decltype(nb)::value>, dim3(tail_grid(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x,
+                       (const float*)eps, (float*)ring, (const float*)sigma, (const float*)row, (const int*)step, scale, sim, order, (float*)out,
                        (long)n);
   });
   CD360_LAUNCH_CHECK();

@@ -1,20 +1,25 @@
 #!/usr/bin/env python
-"""Euler against DPM++ 2M, ancestral Euler, Heun and churned Euler through cd360.job.Sampler: the figures of DESIGN.md's sections on the
+"""Euler against DPM++ 2M, ancestral Euler, Heun, churned Euler, DPM++ 2S ancestral and linear multistep through cd360.job.Sampler: the figures of DESIGN.md's sections on the
 further solvers.  Calls the job sampler directly (bench.py keeps measuring the Euler headline).
 
-  --solver euler|dpmpp2m|euler_a|heun   which step (euler also runs on a checkout that predates the `solver` argument: --repo PATH imports
-                           that checkout); euler_a and every churned run: seed 360 on both routes
+  --solver euler|dpmpp2m|euler_a|heun|dpmpp2s_a|lms   which step (euler also runs on a checkout that predates the `solver` argument: --repo
+                           PATH imports that checkout); euler_a, dpmpp2s_a and every churned run: seed 360 on both routes
+  --eta                    the eta of the ancestral solvers' constructors, for --solver euler_a and dpmpp2s_a (default 1.0)
+  --order                  the order of LinearMultistepSampler's constructor, for --solver lms (default 4)
   --s-churn / --s-tmin / --s-tmax / --s-noise   the churn of EDMSampler's constructor, for --solver euler and heun (default: none)
   --branches 2|3           which guider
   --what deviation         n_steps = 4, all 4 steps at latent 32 / 6 views: the captured job sampler against the un-captured module route
-                           (cd360.sampler's EulerEDMSampler / DPMPP2MSampler / EulerAncestralSampler / HeunEDMSampler + the guider + DiscreteDenoiser around the same UNet, eager),
+                           (cd360.sampler's EulerEDMSampler / DPMPP2MSampler / EulerAncestralSampler / HeunEDMSampler / DPMPP2SAncestralSampler /
+                           LinearMultistepSampler + the guider + DiscreteDenoiser around the same UNet, eager),
                            max |difference| / max |module-route latent|: the yardstick and the figure of
                            tests/test_dpmpp2m_gpu.py::test_dpmpp2m_job_agrees_with_the_uncaptured_module_route and
                            tests/test_euler_a_gpu.py::test_euler_a_job_agrees_with_the_uncaptured_module_route and
-                           tests/test_edm_gpu.py::test_edm_job_agrees_with_the_uncaptured_module_route
+                           tests/test_edm_gpu.py::test_edm_job_agrees_with_the_uncaptured_module_route and
+                           tests/test_highorder_gpu.py::test_highorder_job_agrees_with_the_uncaptured_module_route
   --what timing            steady-step replay time of the graph sampler under Euler AND --solver in this process (median of --reps replays after
                            warm-up, interleaved), at --latent / --refs (default 128 / 50); a Heun steady step holds two
-                           evaluations (compare with two Euler steps), a churned Euler step one launch more than the plain one
+                           evaluations (compare with two Euler steps), as does a DPM++ 2S step; a churned Euler step one launch more than
+                           the plain one
 Prints one JSON line per figure."""
 import argparse
 import json
@@ -23,7 +28,9 @@ import statistics
 import sys
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--solver", default="dpmpp2m", choices=("euler", "dpmpp2m", "euler_a", "heun"))
+ap.add_argument("--solver", default="dpmpp2m", choices=("euler", "dpmpp2m", "euler_a", "heun", "dpmpp2s_a", "lms"))
+ap.add_argument("--eta", type=float, default=1.0)
+ap.add_argument("--order", type=int, default=4)
 ap.add_argument("--s-churn", type=float, default=0.0)
 ap.add_argument("--s-tmin", type=float, default=0.0)
 ap.add_argument("--s-tmax", type=float, default=float("inf"))
@@ -67,8 +74,12 @@ def batch(p, latent, refs):
 
 def make(net, pose, ctx, y, n_steps, solver, churn=None):
     kw = {} if solver == "euler" else {"solver": solver}  # (a checkout that predates the argument serves Euler)
-    if solver == "euler_a" or churn:
+    if solver in ("euler_a", "dpmpp2s_a") or churn:
         kw["seed"] = SEED
+    if solver in ("euler_a", "dpmpp2s_a") and args.eta != 1.0:
+        kw["eta"] = args.eta
+    if solver == "lms":
+        kw["order"] = args.order
     kw.update(churn or {})
     return job.Sampler(net, pose, ctx, y, n_steps, scale_im=SCALE_IM, use_graph=True, **kw)
 
@@ -86,8 +97,11 @@ def deviation():
     got = job.sample_assigned(smp, [(pose, ctx, y, x0)], steps)[0]
     gcfg = ({"target": "sgm.modules.diffusionmodules.guiders.VanillaCFGImgRef", "params": {"scale": 7.5}} if NB == 2 else
             {"target": "sgm.modules.diffusionmodules.guiders.ScheduledCFGImgTextRef", "params": {"scale": 7.5, "scale_im": 3.5}})
-    if args.solver == "euler_a":
-        mod = S.EulerAncestralSampler(num_steps=steps, guider_config=gcfg, device=DEV, seed=SEED)
+    if args.solver in ("euler_a", "dpmpp2s_a"):
+        cls = S.EulerAncestralSampler if args.solver == "euler_a" else S.DPMPP2SAncestralSampler
+        mod = cls(eta=args.eta, num_steps=steps, guider_config=gcfg, device=DEV, seed=SEED)
+    elif args.solver == "lms":
+        mod = S.LinearMultistepSampler(order=args.order, num_steps=steps, guider_config=gcfg, device=DEV)
     elif args.solver == "heun" or CHURN:
         mod = (S.HeunEDMSampler if args.solver == "heun" else S.EulerEDMSampler)(num_steps=steps, guider_config=gcfg, device=DEV, seed=SEED, **CHURN)
     else:
@@ -99,15 +113,18 @@ def deviation():
     network = lambda x_in, t, cond: (net(x_in, timesteps=t, context=cond["crossattn"], y=cond["vector"], pose=pose)[0], None, None, None)  # noqa: E731
     denoiser = lambda inp, sig, cond: den(network, inp, sig, cond)  # noqa: E731
     sig = mod.discretization(steps, device=DEV)
-    x, old = x0.clone(), None
+    x, old, ds = x0.clone(), None, []
+    table = S.lms_coefficients(sig, args.order) if args.solver == "lms" else None
     for i in range(steps):
         s, sn = sig[i].reshape(1), sig[i + 1].reshape(1)
         if args.solver == "heun" or CHURN:
             x, _ = mod.sampler_step(s, sn, denoiser, x, c, uc, mod.gamma_of(sig[i], steps))
         elif args.solver == "euler":
             x, _ = mod.sampler_step(s, sn, denoiser, x, c, uc)
-        elif args.solver == "euler_a":
+        elif args.solver in ("euler_a", "dpmpp2s_a"):
             x = mod.sampler_step(s, sn, denoiser, x, c, uc)
+        elif args.solver == "lms":
+            x = mod.sampler_step(ds, [float(table[i, j]) for j in range(min(i + 1, args.order))], s, denoiser, x, c, uc)
         else:
             x, old = mod.sampler_step(old, None if i == 0 else sig[i - 1].reshape(1), s, sn, denoiser, x, c, uc)
     sampling.clear_rendered_feat(net)
