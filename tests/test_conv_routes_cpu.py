@@ -10,7 +10,8 @@ import itertools
 
 import pytest
 
-from conv_shapes import BATCHES, UNET_3X3, UNET_ROUTES, UNET_UP2X, UNET_UP2X_TILINGS, VAE_3X3, VAE_UP2X
+from conv_shapes import (BATCHES, DGRAD_BATCHES, DGRAD_SCALES, UNET_3X3, UNET_DGRAD, UNET_ROUTES, UNET_UP2X, UNET_UP2X_TILINGS, VAE_3X3,
+                         VAE_UP2X)
 
 # pixels per statistics slab = 32 * the NMB template argument of each tiling's kernel (csrc/gemm8p.hip: launch_conv, launch_128x4)
 SLAB_OF_TILING = {1: 64, 2: 64, 3: 128, 4: 64, 5: 64, 6: 32}
@@ -23,7 +24,9 @@ VAE = [(1, h, h, cin, cout) for h, cin, cout, _, _ in VAE_3X3]
 EDGES = [(2, 9, 7, 128, 320), (3, 16, 8, 64, 320), (1, 16, 16, 64, 48), (2, 16, 24, 192, 1280), (2, 32, 32, 1280, 256), (1, 64, 64, 640, 80),
          (2, 8, 16, 192, 128), (1, 8, 8, 64, 640), (2, 4, 32, 384, 320), (1, 2, 64, 64, 640), (1, 16, 16, 64, 80), (24, 32, 32, 1280, 1280),
          (1, 1, 1, 64, 16), (3, 10, 10, 64, 320), (1, 8, 8, 32, 64)]
-SHAPES = UNET + VAE + EDGES
+# the data-gradient launches of the same convolutions (cd360.grad.ConvIgemmFn: channel counts swapped, Cout' up to 2560), both latent sizes
+DGRAD = sorted({(n, h // sc, h // sc, ci, co) for n in DGRAD_BATCHES for sc in DGRAD_SCALES for h, ci, co, taps, _ in UNET_DGRAD if taps == 9})
+SHAPES = UNET + VAE + EDGES + [s for s in DGRAD if s not in UNET]
 
 
 def halo_fits(N, H, W, Cin):

@@ -397,6 +397,13 @@ for halo in (-1, 1):
     add(f"conv-dma-cfg6-{h}-stats-3x128x128x320x320", conv_dma_case(3, 128, 128, 320, 320, True), ["cd360_conv3x3_dma_bf16"],
         tuning=dict(conv_cfg=6, conv_halo=halo))
     add(f"conv-dma-auto-{h}-stats-3x32x32x1280x1280", conv_dma_case(3, 32, 32, 1280, 1280, True), ["cd360_conv3x3_dma_bf16"], tuning=dict(conv_halo=halo))
+# the data gradient's channel counts (tests/conv_shapes.py UNET_DGRAD: Cout' = the forward Cin): three and six 320-channel tiles on tilings
+# 1 and 6, 3.75 and 7.5 256-channel tiles on tiling 3, each also on the halo form
+for cout in (960, 1920):
+    for cfg in (1, 3, 6):
+        for halo in (0, 1):
+            add(f"conv-dma-cfg{cfg}-{'halo' if halo else 'taps'}-stats-2x16x8x64x{cout}", conv_dma_case(2, 16, 8, 64, cout, True),
+                ["cd360_conv3x3_dma_bf16"], tuning=dict(conv_cfg=cfg, conv_halo=halo))
 
 
 def conv_igemm_case(N, H, W, Cin, Cout, extras, want_stats, stride=1):
@@ -447,6 +454,7 @@ add("conv-module-padded-320-to-4", conv_module_case(2, 16, 16, 320, 4, 1, False)
 for N, H, Wd, cin, cout, stride in ((2, 16, 16, 64, 64, 1), (3, 32, 32, 320, 320, 2), (2, 16, 16, 320, 4, 1)):
     add(f"conv-data-gradient-{N}x{H}x{Wd}x{cin}x{cout}-s{stride}", conv_module_case(N, H, Wd, cin, cout, stride, True), ["cd360_conv_igemm_bf16"],
         grad=True)
+add("conv-data-gradient-2x16x8x1920x128-s1", conv_module_case(2, 16, 8, 1920, 128, 1, True), ["cd360_conv_igemm_bf16"], grad=True)  # Cout' = 1920
 
 
 def conv_up2x_case(N, H, W, Cin, Cout):
