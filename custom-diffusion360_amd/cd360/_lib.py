@@ -112,22 +112,20 @@ SIGNATURES = {
     "cd360_dropout_tick": (c_int, [_P, _P]),
 }
 
-# include/cd360_solvers.h: sampler steps beyond Euler.  A table of its own -- SIGNATURES stays the list of include/cd360_hip.h -- bound and
-# symbol-checked by load() exactly like it.
+# include/cd360_solvers.h: sampler steps beyond Euler.  A table of its own: SIGNATURES stays the list of include/cd360_hip.h.
 SOLVER_SIGNATURES = {
     "cd360_cfg_dpmpp2m_step_f32": (c_int, [_P, _P, _P, _P, _P, c_float, c_float, _P, _P, c_int64, _P]),
     "cd360_cfg_dpmpp2m_step_cl": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_float, c_int, c_int64, c_int, _P]),
 }
 
-# include/cd360_stochastic.h: device noise and the stochastic sampler steps on it.  A third table, bound and symbol-checked like the others.
+# include/cd360_stochastic.h: device noise and the stochastic sampler steps on it.
 STOCHASTIC_SIGNATURES = {
     "cd360_sampler_noise_f32": (c_int, [_P, _P, _P, _P, c_int, c_int64, _P]),
     "cd360_cfg_euler_ancestral_step_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_float, c_float, _P, c_int, c_int64, _P]),
     "cd360_cfg_euler_ancestral_step_cl": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_float, c_float, c_int, c_int64, c_int, _P]),
 }
 
-# include/cd360_edm.h: churn, and the predictor / corrector tails of the EDM family (EulerEDMSampler with s_churn, HeunEDMSampler).  A fourth
-# table, bound and symbol-checked like the others.
+# include/cd360_edm.h: churn, and the predictor / corrector tails of the EDM family (EulerEDMSampler with s_churn, HeunEDMSampler).
 EDM_SIGNATURES = {
     "cd360_edm_churn_f32": (c_int, [_P, _P, _P, _P, _P, c_int, c_int64, _P]),
     "cd360_cfg_edm_predict_cl": (c_int, [_P, _P, _P, _P, c_float, c_float, _P, _P, c_int, c_int64, c_int, _P]),
@@ -136,8 +134,7 @@ EDM_SIGNATURES = {
     "cd360_cfg_edm_correct_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_float, _P, c_int64, _P]),
 }
 
-# include/cd360_highorder.h: the tails of DPM++ 2S ancestral (midpoint, step) and of the linear multistep solver.  A fifth table, bound and
-# symbol-checked like the others.
+# include/cd360_highorder.h: the tails of DPM++ 2S ancestral (midpoint, step) and of the linear multistep solver.
 HIGHORDER_SIGNATURES = {
     "cd360_cfg_dpmpp2s_mid_cl": (c_int, [_P, _P, _P, _P, _P, c_float, c_float, _P, c_int, c_int64, c_int, _P]),
     "cd360_cfg_dpmpp2s_mid_f32": (c_int, [_P, _P, _P, _P, c_float, c_float, _P, c_int64, _P]),
@@ -146,6 +143,10 @@ HIGHORDER_SIGNATURES = {
     "cd360_cfg_lms_step_cl": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_float, c_int, c_int, c_int64, c_int, _P]),
     "cd360_cfg_lms_step_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_float, c_int, _P, c_int64, _P]),
 }
+
+# the whole C ABI: header under include/ -> its table, in the order the headers were added.  load() binds and symbol-checks every entry.
+ABI = {"cd360_hip.h": SIGNATURES, "cd360_solvers.h": SOLVER_SIGNATURES, "cd360_stochastic.h": STOCHASTIC_SIGNATURES,
+       "cd360_edm.h": EDM_SIGNATURES, "cd360_highorder.h": HIGHORDER_SIGNATURES}
 
 TUNING_FIELDS = ("gemm_cfg", "gemm_group_m", "gemm_movers", "gemm_ksplit", "conv_cfg", "conv_dma", "conv_kgroup", "conv_wide", "conv_wmajor",
                  "conv_split", "attn_smallk", "attn_smallk_wgs", "attn_self", "attn_fast", "nerf_kernel", "qattn_cfg", "whatif", "gemm_small", "qattn_keys16",
@@ -192,8 +193,7 @@ def load(check_symbols: bool = True):
     lib = ctypes.CDLL(LIB_PATH)
     if os.environ.get("CD360_LIB"):
         check_symbols = False  # an explicitly named older / probe build (same-box A/B): entry points it predates stay unbound
-    for name, (res, args) in (*SIGNATURES.items(), *SOLVER_SIGNATURES.items(), *STOCHASTIC_SIGNATURES.items(), *EDM_SIGNATURES.items(),
-                              *HIGHORDER_SIGNATURES.items()):
+    for name, (res, args) in ((name, sig) for table in ABI.values() for name, sig in table.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -18,32 +18,21 @@ from . import shard, solvers
 
 
 class Sampler:
-    """Minimal Euler (DDIM-equivalent, EpsScaling) step with the 3-way image/text CFG of guiders.py:102-133 (uncond | image | image+text)
-    or, for `scale_im is None or scale_im <= 0`, the 2-way VanillaCFGImgRef of guiders.py:136-166 (uncond | image+text) -- the switch of
+    """One sampling step of the pose path under the 3-way image/text CFG of guiders.py:102-133 (uncond | image | image+text) or, for
+    `scale_im is None or scale_im <= 0`, the 2-way VanillaCFGImgRef of guiders.py:136-166 (uncond | image+text) -- the switch of
     sample.py:231-240.  B = guider.branches: `ctx` / `y` hold B bs rows ([uc x bs | . | c x bs] resp. [uc x bs | c x bs]), `pose` B bs camera
     batches, and the UNet runs on B bs images (two branches: a third less work per step, not a duplicated branch).
     With `use_graph` the steady-state step (cached render) and the render step are each captured once into a hipGraph and
     replayed: ~3000 launches per step are then issued by the GPU front end instead of the Python interpreter.
-    `solver`: "euler" (EulerEDMSampler, sampling.py:85-136) or "dpmpp2m" (DPMPP2MSampler, sampling.py:390-465: second order, multistep,
-    the same one UNet evaluation per step); the step's tail kernel is the only difference.  DPM++ 2M carries the previous step's denoised
-    latent in `self.gd`, so `step(x, i)` for i > 0 must follow `step(., i - 1)` of the SAME image (`eps()` is unaffected).
-    "euler_a" (EulerAncestralSampler, sampling.py:236-273, 340-347: stochastic, `eta` / `s_noise` as the reference's constructor takes them)
-    draws its noise INSIDE the tail kernel as a pure function of (`seed`, the row's noise stream, step index, channel, pixel)
+    `solver` names the update, one class of cd360/solvers.py each, whose docstring says what it computes and what it carries between steps:
+    "euler" (Euler; ChurnedEuler as soon as `s_churn` > 0, with `s_tmin` / `s_tmax` / `s_noise` as EDMSampler's constructor takes them),
+    "dpmpp2m" (DPMPP2M), "euler_a" (EulerAncestral: `eta` / `s_noise`), "heun" (Heun: churn as for Euler), "dpmpp2s_a" (DPMPP2SAncestral:
+    `eta` / `s_noise`) and "lms" (LMS: `order` in 1..4).  The multistep solvers ("dpmpp2m", "lms") keep earlier steps' results, which are
+    not reset between images: `step(x, i)` for i > 0 must follow `step(., i - 1)` of the SAME image (`eps()` is unaffected).
+    A solver that draws noise draws it INSIDE its kernels as a pure function of (`seed`, the row's noise stream, step index, channel, pixel)
     (include/cd360_stochastic.h), so graph, eager, fresh and un-staged runs add the same bits and no state is kept between steps.
     `noise_streams`: one id per replay row (default: stream 0 everywhere -- all poses of a job share the injected noise, as
-    sample.py:290-292 shares the start noise); `reseed` / `set_noise_streams` rewrite the device buffers, no re-capture.
-    `s_churn` / `s_tmin` / `s_tmax` (with `s_noise`) as EDMSampler's constructor takes them (sampling.py:85-136): with s_churn > 0
-    solver="euler" runs the churned step of include/cd360_edm.h -- noise in front of the UNet on the rows of the window, the UNet at the
-    snapped sigma_hat, the Euler step from sigma_hat -- and `seed` / `noise_streams` / `reseed` / `set_noise_streams` apply to it; with
-    s_churn = 0 it is the step it has always been.  "heun" (HeunEDMSampler, sampling.py:321-337, churn as for Euler) evaluates the UNet
-    twice per step inside ONE captured graph and once on the sigma_next = 0 step, which has a graph of its own; `self.gxe` / `self.gdir`
-    hold the predictor's latent and direction between the two evaluations.
-    "dpmpp2s_a" (DPMPP2SAncestralSampler, sampling.py:350-387; `eta` / `s_noise` / `seed` / `noise_streams` as for "euler_a") evaluates the
-    UNet at (x, sigma) and at the midpoint (`self.gx2`, sigma_mid snapped to the denoiser's grid) inside ONE captured graph
-    (include/cd360_highorder.h); the rows with sigma_down = 0 -- the last, and for eta > 1 interior rows (`self.single_rows`) -- are the
-    ancestral Euler step with one evaluation, on the one-evaluation graph.  "lms" (LinearMultistepSampler, sampling.py:276-311, `order` in
-    1..4) keeps the last `order` directions in the ring `self.gds`; like DPM++ 2M's `gd` it is not reset between images, so `step(x, i)` for
-    i > 0 must follow `step(., i - 1)` of the SAME image."""
+    sample.py:290-292 shares the start noise); `reseed` / `set_noise_streams` rewrite the device buffers, no re-capture."""
 
     SOLVERS = tuple(solvers.SOLVERS)
     EDM_SOLVERS = tuple(k for k in solvers.EDM_SOLVERS if k not in solvers.SOLVERS)  # the names only the EDM registry serves
@@ -52,16 +41,11 @@ class Sampler:
     def __init__(self, net, pose, ctx, y, n_steps, scale=7.5, scale_im=3.5, use_graph=False, prefetch=None, graph_render=True, solver="euler",
                  eta=1.0, s_noise=1.0, seed=0, noise_streams=None, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), order=4):
         from cd360 import sampler as S
-        names = self.SOLVERS + self.EDM_SOLVERS + self.HIGHORDER_SOLVERS
-        if solver not in names:
-            raise ValueError(f"solver {solver!r}: the job sampler serves {', '.join(names)}")
+        if solver not in solvers.NAMES:
+            raise ValueError(f"solver {solver!r}: the job sampler serves {', '.join(solvers.NAMES)}")
         if solver == "lms" and (isinstance(order, bool) or not isinstance(order, int) or not 1 <= order <= 4):
             raise ValueError(f"order {order!r}: the linear multistep solver serves orders 1..4")
-        # the name, and what only that solver knows (cd360/solvers.py): the EDM registry serves its own names, and every name it shares with
-        # the first one as soon as the schedule churns
-        edm = solver in solvers.EDM_SOLVERS and (solver not in solvers.SOLVERS or s_churn > 0)
-        registry = solvers.HIGHORDER_SOLVERS if solver in solvers.HIGHORDER_SOLVERS else solvers.EDM_SOLVERS if edm else solvers.SOLVERS
-        self.solver, self._solver, self.order = solver, registry[solver], order
+        self.solver, self._solver, self.order = solver, solvers.select(solver, s_churn), order  # the name, and what only that solver knows
         self.eta, self.s_noise, self.seed, self.noise_streams = eta, s_noise, seed, noise_streams
         self.s_churn, self.s_tmin, self.s_tmax = s_churn, s_tmin, s_tmax
         self.last_row = False  # True while the step at hand is a one-evaluation row of a two-evaluation solver (Solver.single_row)
@@ -84,9 +68,7 @@ class Sampler:
         self.sigmas = S.LegacyDDPMDiscretization()(n_steps, device=dev)  # n_steps + 1 values, last = 0
         # conditioning is constant over a trajectory: the guider's (uc, uc, c) / (uc, c) batch is assembled once per image, not per step
         self.bs = bs = ctx.shape[0] // nb  # diffusion samples (target poses) per replay: ctx / y hold [uc x bs | . | c x bs] / [uc x bs | c x bs]
-        c = {"crossattn": ctx[(nb - 1) * bs:], "vector": y[(nb - 1) * bs:]}
-        uc = {"crossattn": ctx[:bs], "vector": y[:bs]}
-        _, _, cond3 = self.guider.prepare_inputs(ctx.new_zeros(bs, 1), ctx.new_zeros(bs), c, uc)
+        cond3 = self._cond_batch(ctx, y)
         self.ctx, self.y = cond3["crossattn"].contiguous(), cond3["vector"].contiguous()
         self.prefetch = prefetch  # cd360.prefetch.WeightPrefetcher or None: armed around both captures
         self.use_graph, self.graph, self.lgraph, self._prepared = use_graph, None, None, False
@@ -106,14 +88,18 @@ class Sampler:
         from cd360 import sampling
         sampling.set_cfg_branches(self.net, self.branches)
 
+    def _cond_batch(self, ctx, y):
+        """The guider's conditioning batch ((uc, uc, c) resp. (uc, c) rows) from ctx / y = [uc x bs | . | c x bs] resp. [uc x bs | c x bs]."""
+        bs, nb = self.bs, self.branches
+        c = {"crossattn": ctx[(nb - 1) * bs:], "vector": y[(nb - 1) * bs:]}
+        uc = {"crossattn": ctx[:bs], "vector": y[:bs]}
+        return self.guider.prepare_inputs(ctx.new_zeros(bs, 1), ctx.new_zeros(bs), c, uc)[2]
+
     def retarget(self, pose, ctx, y):
         """Point the sampler at another target pose / conditioning (the next pose of this rank's share).  The captured graphs read both
         through fixed device buffers, so the new values are copied INTO them: the CFG conditioning batch, and the packed
         [B bs, n+1, 16] camera tensor this sampler owns (sgm/modules/utils_cameraray.py::PoseBuffer)."""
-        bs, nb = self.bs, self.branches
-        c = {"crossattn": ctx[(nb - 1) * bs:], "vector": y[(nb - 1) * bs:]}
-        uc = {"crossattn": ctx[:bs], "vector": y[:bs]}
-        _, _, cond3 = self.guider.prepare_inputs(ctx.new_zeros(bs, 1), ctx.new_zeros(bs), c, uc)
+        cond3 = self._cond_batch(ctx, y)
         self.ctx.copy_(cond3["crossattn"])
         self.y.copy_(cond3["vector"])
         if self.use_graph:

@@ -1244,12 +1244,28 @@ def _cfg_cl_args(x: torch.Tensor, eps_cl: torch.Tensor, step_tab: torch.Tensor, 
     return bs, hw, ld, float("nan") if nb == 2 else float(scale_im)
 
 
+def _like(x: torch.Tensor, *ts: torch.Tensor):  # fp32 contiguous, shaped like x
+    assert all(t.dtype == torch.float32 and t.shape == x.shape and t.is_contiguous() for t in ts)
+
+
+def _tab_like(ref: torch.Tensor, *tabs: torch.Tensor):  # a solver's table beside the table `ref` the step's row is picked from
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.shape == ref.shape for t in tabs)
+
+
+def _row4(*rows: torch.Tensor):  # one 4-float row of a table
+    assert all(row.dtype == torch.float32 and row.numel() == 4 and row.is_contiguous() for row in rows)
+
+
+def _scalar(*ts: torch.Tensor):  # a 1-element fp32 tensor (sigma)
+    assert all(t.dtype == torch.float32 and t.numel() == 1 for t in ts)
+
+
 def cfg_euler_step(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, sigma_next: torch.Tensor, scale: float, scale_im: Optional[float]):
     """x [n,...] fp32, eps [3n,...] fp32 (u | ic | c) or, with scale_im=None, [2n,...] (u | c), sigma / sigma_next 0-d fp32 device tensors
     -> Euler-updated x (one kernel)."""
     _need_gpu(x, eps, sigma, sigma_next)
     sim = _cfg_flat_args(x, eps, scale_im)
-    assert sigma.dtype == torch.float32 and sigma_next.dtype == torch.float32 and sigma.numel() == 1 and sigma_next.numel() == 1
+    _scalar(sigma, sigma_next)
     out = torch.empty_like(x)
     check(_lib.load().cd360_cfg_euler_step_f32(_ptr(x), _ptr(eps), _ptr(sigma), _ptr(sigma_next), float(scale), sim, _ptr(out), x.numel(),
                                               _stream()), "cd360_cfg_euler_step_f32")
@@ -1291,8 +1307,9 @@ def cfg_dpmpp2m_step(x: torch.Tensor, eps: torch.Tensor, old: torch.Tensor, sigm
     tensors.  `old` is not read when m4 == 0."""
     _need_gpu(x, eps, old, sigma, mult)
     sim = _cfg_flat_args(x, eps, scale_im)
-    assert old.dtype == torch.float32 and old.shape == x.shape and old.is_contiguous()
-    assert sigma.dtype == torch.float32 and sigma.numel() == 1 and mult.dtype == torch.float32 and mult.numel() == 4 and mult.is_contiguous()
+    _like(x, old)
+    _scalar(sigma)
+    _row4(mult)
     out, old_out = torch.empty_like(x), torch.empty_like(x)
     check(_lib.load().cd360_cfg_dpmpp2m_step_f32(_ptr(x), _ptr(eps), _ptr(old), _ptr(sigma), _ptr(mult), float(scale), sim, _ptr(out),
                                                 _ptr(old_out), x.numel(), _stream()), "cd360_cfg_dpmpp2m_step_f32")
@@ -1306,8 +1323,8 @@ def cfg_dpmpp2m_step_cl(x: torch.Tensor, old: torch.Tensor, eps_cl: torch.Tensor
     when m4 == 0."""
     _need_gpu(x, old, eps_cl, step_tab, mult_tab, step)
     bs, hw, ld, sim = _cfg_cl_args(x, eps_cl, step_tab, step, scale_im)
-    assert old.dtype == torch.float32 and old.shape == x.shape and old.is_contiguous()
-    assert mult_tab.dtype == torch.float32 and mult_tab.is_contiguous() and mult_tab.shape == step_tab.shape
+    _like(x, old)
+    _tab_like(step_tab, mult_tab)
     check(_lib.load().cd360_cfg_dpmpp2m_step_cl(_ptr(x), _ptr(old), _ptr(eps_cl), _ptr(step_tab), _ptr(mult_tab), _ptr(step), float(scale), sim,
                                                bs, hw, ld, _stream()), "cd360_cfg_dpmpp2m_step_cl")
     return x
@@ -1338,7 +1355,8 @@ def cfg_euler_ancestral_step(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Te
     _need_gpu(x, eps, sigma, anc, seed, streams, step)
     sim = _cfg_flat_args(x, eps, scale_im)
     assert x.ndim == 4 and x.shape[1] == 4
-    assert sigma.dtype == torch.float32 and sigma.numel() == 1 and anc.dtype == torch.float32 and anc.numel() == 4 and anc.is_contiguous()
+    _scalar(sigma)
+    _row4(anc)
     bs = x.shape[0]
     _noise_args(seed, streams, step, bs)
     out = torch.empty_like(x)
@@ -1355,16 +1373,12 @@ def cfg_euler_ancestral_step_cl(x: torch.Tensor, eps_cl: torch.Tensor, step_tab:
     sampler_noise(seed, streams, step, ...) drawn inside the kernel (none when sigma_up == 0)."""
     _need_gpu(x, eps_cl, step_tab, anc_tab, step, seed, streams)
     bs, hw, ld, sim = _cfg_cl_args(x, eps_cl, step_tab, step, scale_im)
-    assert anc_tab.dtype == torch.float32 and anc_tab.is_contiguous() and anc_tab.shape == step_tab.shape
+    _tab_like(step_tab, anc_tab)
     _noise_args(seed, streams, step, bs)
     check(_lib.load().cd360_cfg_euler_ancestral_step_cl(_ptr(x), _ptr(eps_cl), _ptr(step_tab), _ptr(anc_tab), _ptr(step), _ptr(seed),
                                                        _ptr(streams), float(scale), sim, bs, hw, ld, _stream()),
           "cd360_cfg_euler_ancestral_step_cl")
     return x
-
-
-def _edm_row(row: torch.Tensor):
-    assert row.dtype == torch.float32 and row.numel() == 4 and row.is_contiguous()
 
 
 def edm_churn(x: torch.Tensor, churn_tab: torch.Tensor, step: torch.Tensor, seed: torch.Tensor, streams: Optional[torch.Tensor]):
@@ -1387,7 +1401,7 @@ def cfg_edm_predict(x: torch.Tensor, eps: torch.Tensor, row: torch.Tensor, scale
     tensors: d = (x - d0) / sigma_hat with d0 combined at sq, xe = x + d (sigma_next - sigma_hat).  want_dir=False: d is not written (None)."""
     _need_gpu(x, eps, row)
     sim = _cfg_flat_args(x, eps, scale_im)
-    _edm_row(row)
+    _row4(row)
     xe = torch.empty_like(x)
     d = torch.empty_like(x) if want_dir else None
     check(_lib.load().cd360_cfg_edm_predict_f32(_ptr(x), _ptr(eps), _ptr(row), float(scale), sim, _ptr(xe), _ptr(d), x.numel(), _stream()),
@@ -1401,8 +1415,7 @@ def cfg_edm_predict_cl(x: torch.Tensor, eps_cl: torch.Tensor, edm_tab: torch.Ten
     (sigma_hat, sigma_next, -, sq) = edm_tab[step]; xe (may BE x: the in-place, churned Euler tail) and d (or None) are written."""
     _need_gpu(x, eps_cl, edm_tab, step, xe, d)
     bs, hw, ld, sim = _cfg_cl_args(x, eps_cl, edm_tab, step, scale_im)
-    for t in (xe,) + (() if d is None else (d,)):
-        assert t.dtype == torch.float32 and t.shape == x.shape and t.is_contiguous()
+    _like(x, xe, *(() if d is None else (d,)))
     check(_lib.load().cd360_cfg_edm_predict_cl(_ptr(x), _ptr(eps_cl), _ptr(edm_tab), _ptr(step), float(scale), sim, _ptr(xe), _ptr(d), bs, hw, ld,
                                               _stream()), "cd360_cfg_edm_predict_cl")
     return xe
@@ -1415,10 +1428,8 @@ def cfg_edm_correct(x: torch.Tensor, xe: torch.Tensor, d: torch.Tensor, eps2: to
     (sigma_next - sigma_hat), a new tensor; xe where sigma_next is not > 0 (eps2 and d are then not read)."""
     _need_gpu(x, xe, d, eps2, row, corr_row)
     sim = _cfg_flat_args(x, eps2, scale_im)
-    _edm_row(row)
-    _edm_row(corr_row)
-    for t in (xe, d):
-        assert t.dtype == torch.float32 and t.shape == x.shape and t.is_contiguous()
+    _row4(row, corr_row)
+    _like(x, xe, d)
     out = torch.empty_like(x)
     check(_lib.load().cd360_cfg_edm_correct_f32(_ptr(x), _ptr(xe), _ptr(d), _ptr(eps2), _ptr(row), _ptr(corr_row), float(scale), sim, _ptr(out),
                                                x.numel(), _stream()), "cd360_cfg_edm_correct_f32")
@@ -1431,22 +1442,11 @@ def cfg_edm_correct_cl(x: torch.Tensor, xe: torch.Tensor, d: torch.Tensor, eps2_
     cfg_euler_step_cl, (sigma_hat, sigma_next) = edm_tab[step][0 / 1], sq' = corr_tab[step][3]; x <- xe where sigma_next is not > 0."""
     _need_gpu(x, xe, d, eps2_cl, edm_tab, corr_tab, step)
     bs, hw, ld, sim = _cfg_cl_args(x, eps2_cl, edm_tab, step, scale_im)
-    for t in (xe, d):
-        assert t.dtype == torch.float32 and t.shape == x.shape and t.is_contiguous()
-    assert corr_tab.dtype == torch.float32 and corr_tab.is_contiguous() and corr_tab.shape == edm_tab.shape
+    _like(x, xe, d)
+    _tab_like(edm_tab, corr_tab)
     check(_lib.load().cd360_cfg_edm_correct_cl(_ptr(x), _ptr(xe), _ptr(d), _ptr(eps2_cl), _ptr(edm_tab), _ptr(corr_tab), _ptr(step), float(scale), sim,
                                               bs, hw, ld, _stream()), "cd360_cfg_edm_correct_cl")
     return x
-
-
-def _like(x: torch.Tensor, *ts: torch.Tensor):
-    for t in ts:
-        assert t.dtype == torch.float32 and t.shape == x.shape and t.is_contiguous()
-
-
-def _tab_like(ref: torch.Tensor, *tabs: torch.Tensor):
-    for t in tabs:
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.shape == ref.shape
 
 
 def cfg_dpmpp2s_mid(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, mult: torch.Tensor, scale: float, scale_im: Optional[float]):
@@ -1455,8 +1455,8 @@ def cfg_dpmpp2s_mid(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, mul
     m2 d0, a new tensor."""
     _need_gpu(x, eps, sigma, mult)
     sim = _cfg_flat_args(x, eps, scale_im)
-    assert sigma.dtype == torch.float32 and sigma.numel() == 1
-    _edm_row(mult)
+    _scalar(sigma)
+    _row4(mult)
     x2 = torch.empty_like(x)
     check(_lib.load().cd360_cfg_dpmpp2s_mid_f32(_ptr(x), _ptr(eps), _ptr(sigma), _ptr(mult), float(scale), sim, _ptr(x2), x.numel(), _stream()),
           "cd360_cfg_dpmpp2s_mid_f32")
@@ -1485,8 +1485,7 @@ def cfg_dpmpp2s_step(x: torch.Tensor, x2: torch.Tensor, eps2: torch.Tensor, mid_
     sim = _cfg_flat_args(x, eps2, scale_im)
     assert x.ndim == 4 and x.shape[1] == 4
     _like(x, x2)
-    for row in (mid_row, mult, anc):
-        _edm_row(row)
+    _row4(mid_row, mult, anc)
     bs = x.shape[0]
     _noise_args(seed, streams, step, bs)
     out = torch.empty_like(x)
@@ -1526,8 +1525,9 @@ def cfg_lms_step(x: torch.Tensor, eps: torch.Tensor, ring: torch.Tensor, sigma: 
     _need_gpu(x, eps, ring, sigma, row, step)
     sim = _cfg_flat_args(x, eps, scale_im)
     order = _lms_ring(x, ring)
-    assert sigma.dtype == torch.float32 and sigma.numel() == 1 and step.dtype == torch.int32 and step.numel() == 1
-    _edm_row(row)
+    _scalar(sigma)
+    assert step.dtype == torch.int32 and step.numel() == 1
+    _row4(row)
     out = torch.empty_like(x)
     check(_lib.load().cd360_cfg_lms_step_f32(_ptr(x), _ptr(eps), _ptr(ring), _ptr(sigma), _ptr(row), _ptr(step), float(scale), sim, order, _ptr(out),
                                             x.numel(), _stream()), "cd360_cfg_lms_step_f32")

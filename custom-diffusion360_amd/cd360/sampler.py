@@ -227,14 +227,7 @@ class EulerEDMSampler(BaseDiffusionSampler):
         self.noise_sampler = (lambda x: torch.randn_like(x)) if seed is None else self._seeded_noise
 
     def _seeded_noise(self, x):
-        if not x.is_cuda:
-            from ._lib import Cd360Error
-            raise Cd360Error(f"the seeded noise of {type(self).__name__} is drawn by a HIP kernel; got a CPU tensor (seed=None draws torch.randn_like)")
-        if self._noise is None or self._noise.seed.device != x.device:
-            self._noise = DeviceNoise(torch.tensor([seed_words(self.seed)], dtype=torch.int64, device=x.device), None,
-                                      torch.zeros(1, dtype=torch.int32, device=x.device))
-        self._noise.step.fill_(self._step)
-        return self._noise.draw(x)
+        return seeded_noise(self, x, self._step)
 
     def prepare_sampling_loop(self, x, cond, uc=None, num_steps=None):
         self._step = 0
@@ -490,6 +483,13 @@ def get_ancestral_step(sigma_from, sigma_to, eta=1.0):
     return sigma_down, sigma_up
 
 
+def snap_c_in(denoiser: "DiscreteDenoiser", grid: torch.Tensor, s: torch.Tensor):
+    """(c_in(sq), sq) on the host, sq = s snapped to `grid` (the denoiser's sigmas in CPU fp32) as DiscreteDenoiser.possibly_quantize_sigma
+    snaps it, c_in the denoiser's own scaling of it: what the table builders below put into columns 2 and 3."""
+    sq = grid[(s - grid[:, None]).abs().argmin(dim=0).view(s.shape)]
+    return denoiser.scaling(sq)[2], sq
+
+
 def seed_words(seed: int) -> int:
     """Any Python int -> the int64 whose 64 bits are the seed's low 64 bits (the device buffer's dtype; the Philox key is its two halves)."""
     s = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -506,6 +506,19 @@ class DeviceNoise:
     def draw(self, x: torch.Tensor) -> torch.Tensor:
         from . import ops
         return ops.sampler_noise(self.seed, self.streams, self.step, x.shape[0], x.shape[2], x.shape[3])
+
+
+def seeded_noise(sampler, x: torch.Tensor, step: int) -> torch.Tensor:
+    """The seed=<int> noise_sampler of the sampler classes: one draw of the library's generator under `sampler.seed`, stream 0 and the step
+    word `step`, which the caller counts by its own rule (see the class docstrings); the DeviceNoise is kept on `sampler._noise` per device."""
+    if not x.is_cuda:
+        from ._lib import Cd360Error
+        raise Cd360Error(f"the seeded noise of {type(sampler).__name__} is drawn by a HIP kernel; got a CPU tensor (seed=None draws torch.randn_like)")
+    if sampler._noise is None or sampler._noise.seed.device != x.device:
+        sampler._noise = DeviceNoise(torch.tensor([seed_words(sampler.seed)], dtype=torch.int64, device=x.device), None,
+                                     torch.zeros(1, dtype=torch.int32, device=x.device))
+    sampler._noise.step.fill_(step)
+    return sampler._noise.draw(x)
 
 
 class EulerAncestralSampler(BaseDiffusionSampler):
@@ -530,15 +543,9 @@ class EulerAncestralSampler(BaseDiffusionSampler):
         self.noise_sampler = (lambda x: torch.randn_like(x)) if seed is None else self._seeded_noise
 
     def _seeded_noise(self, x):
-        if not x.is_cuda:
-            from ._lib import Cd360Error
-            raise Cd360Error(f"the seeded noise of {type(self).__name__} is drawn by a HIP kernel; got a CPU tensor (seed=None draws torch.randn_like)")
-        if self._noise is None or self._noise.seed.device != x.device:
-            self._noise = DeviceNoise(torch.tensor([seed_words(self.seed)], dtype=torch.int64, device=x.device), None,
-                                      torch.zeros(1, dtype=torch.int32, device=x.device))
-        self._noise.step.fill_(self._draws)
+        z = seeded_noise(self, x, self._draws)
         self._draws += 1
-        return self._noise.draw(x)
+        return z
 
     def euler_step(self, x, d, dt):
         return x + dt * d
@@ -579,6 +586,31 @@ def euler_ancestral_table(sigmas: torch.Tensor, eta: float = 1.0, s_noise: float
     return torch.stack([down, up, torch.full_like(down, float(s_noise)), torch.zeros_like(down)], 1).contiguous()
 
 
+def ancestral_finish(x: torch.Tensor, anc_row: torch.Tensor, noise, fused: bool, kernel: Callable, plain: Callable) -> torch.Tensor:
+    """End an update x_n with the ancestral noise of (sigma_down, sigma_up, s_noise, 0) = anc_row: x_n if sigma_up == 0 else x_n + (z * s_noise)
+    * sigma_up, for every form of `noise`.  `kernel(ops, anc, n)` launches the solver's fused tail on a 4-element row and a DeviceNoise;
+    `plain(sigma_down)` is its update in plain torch without the noise.  A DeviceNoise, fused: ONE launch that draws z itself.  A tensor z
+    (a caller's own draw), fused: the kernel's sigma_up = 0 form on a throw-away DeviceNoise, then z added by torch in the kernel's order.
+    Otherwise plain torch; None is fine where sigma_up == 0."""
+    if fused and x.is_cuda:
+        from . import ops
+        if isinstance(noise, DeviceNoise):  # (nothing read back: this is the call a captured un-staged step makes)
+            return kernel(ops, anc_row.reshape(4), noise)
+    sd, su, s_noise, _ = anc_row.reshape(4).unbind()
+    noisy = float(su) != 0.0
+    if noisy and noise is None:
+        raise ValueError("sigma_up != 0: the step needs `noise` (a DeviceNoise or a tensor shaped like x)")
+    if fused and x.is_cuda:
+        dry = DeviceNoise(torch.zeros(1, dtype=torch.int64, device=x.device), None, torch.zeros(1, dtype=torch.int32, device=x.device))
+        x_n = kernel(ops, torch.stack([sd, torch.zeros_like(su), s_noise, torch.zeros_like(su)]), dry)
+        return x_n + (noise * s_noise) * su if noisy else x_n
+    x_n = plain(sd)
+    if not noisy:
+        return x_n
+    z = noise.draw(x) if isinstance(noise, DeviceNoise) else noise
+    return x_n + (z * s_noise) * su
+
+
 def cfg_euler_ancestral_update(x: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor, anc_row: torch.Tensor, scale: float,
                                scale_im: Optional[float] = None, noise=None, fused: bool = True) -> torch.Tensor:
     """One fused tail of a CFG ancestral Euler step with EpsScaling: den_b = x - sigma eps_b, d0 = the guider's combine as in
@@ -588,25 +620,9 @@ def cfg_euler_ancestral_update(x: torch.Tensor, eps: torch.Tensor, sigma: torch.
     sigma_up = 0 form) and the given z is added by torch in the kernel's order; not needed when sigma_up == 0.
     fused=False: the same chain in plain torch, in the kernel's order."""
     cfg_branch_count(x, eps, scale_im)
-    if fused and x.is_cuda and isinstance(noise, DeviceNoise):  # (nothing read back: this is the call a captured un-staged step makes)
-        from . import ops
-        return ops.cfg_euler_ancestral_step(x, eps, sigma, anc_row.reshape(4), noise.seed, noise.streams, noise.step, scale, scale_im)
-    sd, su, s_noise, _ = anc_row.reshape(4).unbind()
-    noisy = float(su) != 0.0
-    if noisy and noise is None:
-        raise ValueError("sigma_up != 0: the step needs `noise` (a DeviceNoise or a tensor shaped like x)")
-    if fused and x.is_cuda:
-        from . import ops
-        dry = DeviceNoise(torch.zeros(1, dtype=torch.int64, device=x.device), None, torch.zeros(1, dtype=torch.int32, device=x.device))
-        x_e = ops.cfg_euler_ancestral_step(x, eps, sigma, torch.stack([sd, torch.zeros_like(su), s_noise, torch.zeros_like(su)]),
-                                           dry.seed, None, dry.step, scale, scale_im)
-        return x_e + (noise * s_noise) * su if noisy else x_e
-    d0 = cfg_combine(x, eps, sigma, scale, scale_im)
-    x_e = x + (x - d0) / sigma * (sd - sigma)
-    if not noisy:
-        return x_e
-    z = noise.draw(x) if isinstance(noise, DeviceNoise) else noise
-    return x_e + (z * s_noise) * su
+    return ancestral_finish(x, anc_row, noise, fused,
+                            lambda ops, anc, n: ops.cfg_euler_ancestral_step(x, eps, sigma, anc, n.seed, n.streams, n.step, scale, scale_im),
+                            lambda sd: x + (x - cfg_combine(x, eps, sigma, scale, scale_im)) / sigma * (sd - sigma))
 
 
 def fused_cfg_euler_ancestral_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, sigma: torch.Tensor, anc_row: torch.Tensor,
@@ -637,18 +653,14 @@ def edm_tables(sigmas: torch.Tensor, denoiser: "DiscreteDenoiser", s_churn: floa
     grid = denoiser.sigmas.detach().to("cpu", torch.float32)
     n = sig.numel() - 1
 
-    def snapped(s):  # DiscreteDenoiser.possibly_quantize_sigma + EpsScaling's c_in, on the host
-        sq = grid[(s - grid[:, None]).abs().argmin(dim=0).view(s.shape)]
-        return denoiser.scaling(sq)[2], sq
-
     edm, corr, churn = [], [], []
     for i in range(n):
         s, sn = sig[i].reshape(1), sig[i + 1].reshape(1)
         gamma = min(s_churn / n, 2 ** 0.5 - 1) if s_tmin <= sig[i] <= s_tmax else 0.0
         s_hat = s * (gamma + 1.0)
         std = (s_hat ** 2 - s ** 2) ** 0.5 if gamma > 0 else torch.zeros(1)
-        c_in, sq = snapped(s_hat)
-        c_in_n, sq_n = snapped(sn)
+        c_in, sq = snap_c_in(denoiser, grid, s_hat)
+        c_in_n, sq_n = snap_c_in(denoiser, grid, sn)
         edm.append(torch.cat([s_hat, sn, c_in, sq]))
         corr.append(torch.cat([sn, sn, c_in_n, sq_n]))
         churn.append(torch.cat([torch.full((1,), float(gamma)), std, torch.full((1,), float(s_noise)), torch.zeros(1)]))
@@ -708,6 +720,16 @@ def cfg_edm_correct(x: torch.Tensor, xe: torch.Tensor, d: torch.Tensor, eps2: to
     return x + (d + d_new) / 2.0 * (sn - sh)
 
 
+def edm_head(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, edm_row: torch.Tensor, churn: torch.Tensor, guider, noise, fused: bool,
+             want_dir: bool = True):
+    """What the Euler and the Heun step of the EDM family begin with: churn, the network at q(sigma_hat), the predictor tail -> (x_hat, x_e, d);
+    d is None for want_dir=False."""
+    scale, scale_im = guider_scales(guider)
+    x_hat = edm_churn(x, churn, noise, fused=fused)
+    eps = cfg_eps(denoiser, network, x_hat, edm_row.reshape(4)[0], guider.branches)
+    return (x_hat,) + cfg_edm_predict(x_hat, eps.contiguous(), edm_row, scale, scale_im, fused=fused, want_dir=want_dir)
+
+
 def fused_cfg_edm_euler_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, edm_row: torch.Tensor, churn: torch.Tensor, guider,
                              noise=None, fused: bool = True) -> torch.Tensor:
     """ONE step of EulerEDMSampler.sampler_step with churn (sampling.py:96-110) in the form the sampling job launches it:
@@ -717,10 +739,7 @@ def fused_cfg_edm_euler_step(denoiser: "DiscreteDenoiser", network: Callable, x:
         x'    = cfg_edm_predict(x_hat, eps, edm_row)[0]    cd360_cfg_edm_predict_f32: c_out at sq, to_d and dt at sigma_hat
 
     `edm_row` = row i of edm_tables(...)[0]; `churn` and `noise` as edm_churn takes them."""
-    scale, scale_im = guider_scales(guider)
-    x_hat = edm_churn(x, churn, noise, fused=fused)
-    eps = cfg_eps(denoiser, network, x_hat, edm_row.reshape(4)[0], guider.branches)
-    return cfg_edm_predict(x_hat, eps.contiguous(), edm_row, scale, scale_im, fused=fused, want_dir=False)[0]
+    return edm_head(denoiser, network, x, edm_row, churn, guider, noise, fused, want_dir=False)[1]
 
 
 def fused_cfg_heun_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, edm_row: torch.Tensor, corr_row: torch.Tensor,
@@ -730,9 +749,7 @@ def fused_cfg_heun_step(denoiser: "DiscreteDenoiser", network: Callable, x: torc
     cfg_edm_correct(x_hat, x_e, d, eps2, edm_row, corr_row): cd360_cfg_edm_correct_f32.  `last`: the host-side skip of the reference
     (sigma_next < 1e-14); None reads it from edm_row (one read-back: a captured step passes the flag)."""
     scale, scale_im = guider_scales(guider)
-    x_hat = edm_churn(x, churn, noise, fused=fused)
-    eps = cfg_eps(denoiser, network, x_hat, edm_row.reshape(4)[0], guider.branches)
-    xe, d = cfg_edm_predict(x_hat, eps.contiguous(), edm_row, scale, scale_im, fused=fused)
+    x_hat, xe, d = edm_head(denoiser, network, x, edm_row, churn, guider, noise, fused)
     if last is None:
         last = float(edm_row.reshape(4)[1]) < 1e-14
     if last:
@@ -805,21 +822,17 @@ def dpmpp2s_tables(sigmas: torch.Tensor, denoiser: "DiscreteDenoiser", eta: floa
     anc = euler_ancestral_table(sig, eta, s_noise)
     one = DPMPP2SAncestralSampler.__new__(DPMPP2SAncestralSampler)
 
-    def snapped(s):  # DiscreteDenoiser.possibly_quantize_sigma + the scaling's c_in, on the host
-        sq = grid[(s - grid[:, None]).abs().argmin(dim=0).view(s.shape)]
-        return denoiser.scaling(sq)[2], sq
-
     mid, mult = [], []
     for i in range(sig.numel() - 1):
         s, sn, sd = sig[i].reshape(1), sig[i + 1].reshape(1), anc[i, 0].reshape(1)
         if float(sd) < 1e-14:
-            c_in, sq = snapped(s)
+            c_in, sq = snap_c_in(denoiser, grid, s)
             mid.append(torch.cat([s, sn, c_in, sq]))
             mult.append(torch.zeros(4))
             continue
         h, sm, t, t_next = one.get_variables(s, sd)
         s_mid = to_sigma(sm)
-        c_in, sq = snapped(s_mid)
+        c_in, sq = snap_c_in(denoiser, grid, s_mid)
         mid.append(torch.cat([s_mid, sd, c_in, sq]))
         mult.append(torch.cat(list(one.get_mult(h, sm, t, t_next))))
     return anc, torch.stack(mid).contiguous(), torch.stack(mult).contiguous()
@@ -851,26 +864,10 @@ def cfg_dpmpp2s_update(x: torch.Tensor, x2: torch.Tensor, eps2: torch.Tensor, mi
     cfg_euler_ancestral_update takes it: a DeviceNoise -- fused: ONE kernel that draws z itself -- or a tensor z shaped like x, added by torch
     in the kernel's order behind the kernel's sigma_up = 0 form.  fused=False: the same chain in plain torch, in the kernel's order."""
     cfg_branch_count(x, eps2, scale_im)
-    if fused and x.is_cuda and isinstance(noise, DeviceNoise):  # (nothing read back: this is the call a captured un-staged step makes)
-        from . import ops
-        return ops.cfg_dpmpp2s_step(x, x2, eps2, mid_row.reshape(4), mult.reshape(4), anc_row.reshape(4), noise.seed, noise.streams, noise.step,
-                                    scale, scale_im)
-    sd, su, s_noise, _ = anc_row.reshape(4).unbind()
-    noisy = float(su) != 0.0
-    if noisy and noise is None:
-        raise ValueError("sigma_up != 0: the step needs `noise` (a DeviceNoise or a tensor shaped like x)")
-    if fused and x.is_cuda:
-        from . import ops
-        dry = DeviceNoise(torch.zeros(1, dtype=torch.int64, device=x.device), None, torch.zeros(1, dtype=torch.int32, device=x.device))
-        x_n = ops.cfg_dpmpp2s_step(x, x2, eps2, mid_row.reshape(4), mult.reshape(4), torch.stack([sd, torch.zeros_like(su), s_noise, torch.zeros_like(su)]),
-                                   dry.seed, None, dry.step, scale, scale_im)
-        return x_n + (noise * s_noise) * su if noisy else x_n
-    m3, m4 = mult.reshape(4)[2], mult.reshape(4)[3]
-    x_n = m3 * x - m4 * cfg_combine(x2, eps2, mid_row.reshape(4)[3], scale, scale_im)
-    if not noisy:
-        return x_n
-    z = noise.draw(x) if isinstance(noise, DeviceNoise) else noise
-    return x_n + (z * s_noise) * su
+    m = mult.reshape(4)
+    return ancestral_finish(x, anc_row, noise, fused,
+                            lambda ops, anc, n: ops.cfg_dpmpp2s_step(x, x2, eps2, mid_row.reshape(4), m, anc, n.seed, n.streams, n.step, scale, scale_im),
+                            lambda sd: m[2] * x - m[3] * cfg_combine(x2, eps2, mid_row.reshape(4)[3], scale, scale_im))
 
 
 def fused_cfg_dpmpp2s_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, sigma: torch.Tensor, anc_row: torch.Tensor,

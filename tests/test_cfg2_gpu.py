@@ -1,20 +1,18 @@
 """Two-way CFG (VanillaCFGImgRef: uncond | image+text) on the captured HIP sampling step: the two-branch forms of the tail kernels, their
 memory safety, the GPU trajectory against the reference's golden, and the sampling job in two-branch mode.  Needs an MI355X."""
+import functools
 import os
-import sys
 
 import pytest
 import torch
 
 import guarded as G
+import sampler_cases as SC
 import weights as W
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from sampler_cases import BF, DEV
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-BF = torch.bfloat16
+R = functools.partial(SC.R, dtype=BF)
 
 # test 9's yardstick: the SAME comparison (captured job sampler against the un-captured module route, 3 steps, latent 32 / 6 views, bs = 1)
 # for THREE branches on the parent commit, measured with tools/cfg_branches_report.py on the box and in the session of this change
@@ -26,11 +24,6 @@ def rel(got, want):
     got, want = got.detach().float().cpu(), want.detach().float().cpu()
     assert got.shape == want.shape and torch.isfinite(got).all()
     return (got - want).abs().max().item() / max(want.abs().max().item(), 1e-12)
-
-
-def R(*shape, seed=0, scale=1.0, dtype=BF):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    return (torch.randn(*shape, generator=g, device=DEV) * scale).to(dtype)
 
 
 # ================================================================================================ 5: the tail kernels
@@ -74,15 +67,7 @@ def test_two_branch_cl_kernel_equals_the_f32_kernel_on_the_same_rows():
 
 def _restated(x, e, s, sn, scale, scale_im):
     """The kernels' expression in the kernels' order, one fp32 rounding per operation (torch's elementwise kernels do not contract)."""
-    if scale_im is None:
-        e_u, e_c = e.chunk(2)
-        du, dc = x - s * e_u, x - s * e_c
-        d0 = du + scale * (dc - du)
-    else:
-        e_u, e_i, e_c = e.chunk(3)
-        du, dic, dc = x - s * e_u, x - s * e_i, x - s * e_c
-        d0 = du + scale * (dc - dic) + scale_im * (dic - du)
-    return x + (x - d0) / s * (sn - s)
+    return x + (x - SC.combine(x, e, s, scale, scale_im)) / s * (sn - s)
 
 
 @pytest.mark.parametrize("scale_im", [3.5, 0.0, -1.25, None])
@@ -121,11 +106,6 @@ def test_both_kernels_equal_a_torch_restatement_in_the_kernels_order(scale_im):
 
 
 # ================================================================================================ 6: guarded runs
-def _guardfn(fn):
-    fn.wants_guard = True
-    return fn
-
-
 @pytest.mark.parametrize("bs,H,Wd", [(1, 5, 7), (2, 24, 40)])
 def test_two_branch_tails_read_two_branches_and_write_their_output_only(bs, H, Wd):
     """Both two-branch tails under tests/guarded.py, both poison patterns.  `eps` lives in arena blocks: once with EXACTLY 2 bs images
@@ -137,7 +117,7 @@ def test_two_branch_tails_read_two_branches_and_write_their_output_only(bs, H, W
              tab=R(5, 4, seed=2, dtype=torch.float32).abs() + 0.5, step=torch.tensor([3], dtype=torch.int32, device=DEV),
              s0=torch.tensor([1.7], device=DEV), s1=torch.tensor([1.1], device=DEV), xc=R(bs, 4, H, Wd, seed=1, dtype=torch.float32))
 
-    @_guardfn
+    @SC.guardfn
     def fn(x, e, e16, tab, step, s0, s1, xc, guard):
         outs = []
         for tail in (0, bs):  # exact allocation; poisoned third behind the two branches
@@ -294,24 +274,14 @@ def test_two_branch_job_agrees_with_the_uncaptured_module_route():
     Measured (MI355X, one session): three branches on the parent commit 3.281e-2 of the latent's maximum (and the same, bit for bit, on
     this tree); two branches 4.114e-2; bar 6.562e-2.  DESIGN.md section 6.1."""
     import bench
-    from cd360 import job, sampling
+    from cd360 import job
     from cd360 import sampler as S
     latent, refs, steps = 32, 6, 3
     net = bench.build_model(latent, refs, 50, DEV)
     pose, ctx, y, x0 = _job2([0], latent, refs)
     got = job.sample_assigned(job.Sampler(net, pose, ctx, y, 50, scale_im=0, use_graph=True), [(pose, ctx, y, x0)], steps)[0]
-    eul = S.EulerEDMSampler(num_steps=50, guider_config={"target": "sgm.modules.diffusionmodules.guiders.VanillaCFGImgRef", "params": {"scale": 7.5}},
-                            device=DEV)
-    den = S.DiscreteDenoiser().to(DEV)
-    sampling.set_cfg_branches(net, 2)
-    sampling.clear_rendered_feat(net)
-    c, uc = {"crossattn": ctx[1:], "vector": y[1:]}, {"crossattn": ctx[:1], "vector": y[:1]}
-    network = lambda x_in, t, cond: (net(x_in, timesteps=t, context=cond["crossattn"], y=cond["vector"], pose=pose)[0], None, None, None)  # noqa: E731
-    sig = eul.discretization(50, device=DEV)
-    x = x0.clone()
-    for i in range(steps):
-        x, _ = eul.sampler_step(sig[i].reshape(1), sig[i + 1].reshape(1), lambda inp, s, cond: den(network, inp, s, cond), x, c, uc)
-    sampling.clear_rendered_feat(net)
+    eul = S.EulerEDMSampler(num_steps=50, guider_config=SC.guider_config(2), device=DEV)
+    x = SC.module_route(net, eul, "euler", 2, pose, ctx, y, x0, steps)
     dev = float((got - x).abs().max() / x.abs().max())
     print("two-branch job vs module route, 3 steps: max abs", float((got - x).abs().max()), "rel", dev, "| parent, three branches:",
           PARENT_CFG3_JOB_VS_MODULE_REL)

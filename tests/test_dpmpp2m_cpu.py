@@ -3,12 +3,12 @@ DPMPP2MSampler (tests/golden/make_golden_dpmpp2m.py: a subclass that only unpack
 signature table, and the job sampler's `solver` argument.  CPU only; tests/test_dpmpp2m_gpu.py holds the kernels and the captured job."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import sampler_cases as SC
 from test_sampler_cpu import dummy_network
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -156,15 +156,12 @@ def test_solver_header_matches_the_second_signature_table():
     to (every `cd360_...(` word, comments included); the library exports both symbols, typed; SIGNATURES does not hold the new names and
     cd360_hip.h does not name them."""
     from cd360 import _lib
-    header = open(os.path.join(ROOT, "include", "cd360_solvers.h")).read()
-    declared = set(re.findall(r"\b(cd360_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(_lib.SOLVER_SIGNATURES) == set(NEW), declared ^ set(_lib.SOLVER_SIGNATURES)
-    assert not set(_lib.SIGNATURES) & set(NEW)
-    assert not any(n in open(os.path.join(ROOT, "include", "cd360_hip.h")).read() for n in NEW)
-    lib = _lib.load(check_symbols=True)
-    for name in NEW:
-        fn = getattr(lib, name)
-        assert isinstance(fn, ctypes._CFuncPtr) and fn.restype is ctypes.c_int and list(fn.argtypes) == _lib.SOLVER_SIGNATURES[name][1]
+    older = ("cd360_hip.h",)
+    mismatch, in_tables, in_headers, mistyped, lib = SC.check_header_matches_table("cd360_solvers.h", _lib.SOLVER_SIGNATURES, NEW, older)
+    assert not mismatch, mismatch
+    assert not in_tables, in_tables
+    assert not in_headers, in_headers
+    assert not mistyped, mistyped
     nul = ctypes.c_void_p(None)  # the host refuses null pointers before anything is launched (no GPU needed)
     assert lib.cd360_cfg_dpmpp2m_step_f32(nul, nul, nul, nul, nul, 7.5, 3.5, nul, nul, 16, nul) == -1
     assert lib.cd360_cfg_dpmpp2m_step_cl(nul, nul, nul, nul, nul, nul, 7.5, 3.5, 1, 16, 4, nul) == -1

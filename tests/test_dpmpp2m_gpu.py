@@ -1,20 +1,13 @@
 """DPM++ 2M on the captured HIP sampling step: the two tail kernels bit for bit against their torch restatement, their memory safety, the
 GPU trajectory against the reference's golden, and the sampling job with solver="dpmpp2m".  Needs an MI355X."""
-import functools
-import os
-import re
-import sys
 
 import pytest
 import torch
 
 import guarded as G
+import sampler_cases as SC
+from sampler_cases import BF, DEV, LATENT, POSES, STEPS, R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-DEV = "cuda"
-BF = torch.bfloat16
 NEW = ["cd360_cfg_dpmpp2m_step_f32", "cd360_cfg_dpmpp2m_step_cl"]
 
 # test 5's yardstick: the SAME comparison (captured job sampler against the un-captured module route, n_steps = 4, all 4 steps, latent 32 /
@@ -27,14 +20,7 @@ PARENT_EULER_JOB_VS_MODULE_REL = 0.05488
 # ================================================================================================ 1: the kernels, bit for bit
 def _restated(x, e, old, s, m, scale, scale_im):
     """The kernels' expression in the kernels' order, one fp32 rounding per operation (torch's elementwise kernels do not contract)."""
-    if scale_im is None:
-        e_u, e_c = e.chunk(2)
-        du, dc = x - s * e_u, x - s * e_c
-        d0 = du + scale * (dc - du)
-    else:
-        e_u, e_i, e_c = e.chunk(3)
-        du, dic, dc = x - s * e_u, x - s * e_i, x - s * e_c
-        d0 = du + scale * (dc - dic) + scale_im * (dic - du)
+    d0 = SC.combine(x, e, s, scale, scale_im)
     m1, m2, m3, m4 = m.unbind()
     dd = d0 if float(m4) == 0.0 else m3 * d0 - m4 * old
     return m1 * x - m2 * dd, d0
@@ -109,16 +95,6 @@ def test_host_refuses_bad_arguments():
 
 
 # ================================================================================================ 2: guarded runs
-def _guardfn(fn):
-    fn.wants_guard = True
-    return fn
-
-
-def R(*shape, seed=0, dtype=torch.float32):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    return torch.randn(*shape, generator=g, device=DEV).to(dtype)
-
-
 GUARDED = []  # (id, declares, bs, H, W, nb, row): what test_every_solver_entry_point_has_a_guarded_case reads
 for _bs, _H, _W in ((1, 5, 7), (2, 24, 40)):
     for _nb in (3, 2):
@@ -140,7 +116,7 @@ def test_tails_write_x_and_old_only_and_never_read_old_on_a_first_row(declares, 
              tab=tab, mult=mult, step=torch.tensor([row], dtype=torch.int32, device=DEV))
     tail = bs if nb == 2 else 0
 
-    @_guardfn
+    @SC.guardfn
     def fn(x, old, e, e16, tab, mult, step, guard):
         ge = guard.torch.empty((nb * bs + tail, 4, H, Wd), dtype=torch.float32, device=DEV)
         ge[:nb * bs].copy_(e)
@@ -172,13 +148,10 @@ def test_every_solver_entry_point_has_a_guarded_case():
     """The twin of test_every_launching_entry_point_has_a_case for include/cd360_solvers.h (runs without a GPU): every `int cd360_...(`
     the header declares is in some guarded case's `declares` in this file, and is typed in SOLVER_SIGNATURES."""
     from cd360 import _lib
-    src = open(os.path.join(ROOT, "include", "cd360_solvers.h")).read()
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    names = set(re.findall(r"\b(?:int|int64_t)\s+(cd360_\w+)\s*\(", src))
-    assert names == set(_lib.SOLVER_SIGNATURES) and names, names ^ set(_lib.SOLVER_SIGNATURES)
-    declared = {e for c in GUARDED for e in c[1]}
-    assert declared <= names, declared - names
-    assert not names - declared, f"launching entry points without a guarded case: {sorted(names - declared)}"
+    untyped, unknown, uncovered = SC.check_guarded_cover("cd360_solvers.h", _lib.SOLVER_SIGNATURES, GUARDED)
+    assert not untyped, untyped
+    assert not unknown, unknown
+    assert not uncovered, f"launching entry points without a guarded case: {sorted(uncovered)}"
 
 
 # ================================================================================================ 3: the GPU trajectory
@@ -202,50 +175,15 @@ def test_fused_step_on_the_gpu_walks_the_reference_trajectory(name):
 
 
 # ================================================================================================ 4, 5: the job
-LATENT, REFS, STEPS, POSES = 32, 6, 4, 3
-
-
-@functools.lru_cache(maxsize=1)
-def _net():
-    import bench
-    return bench.build_model(LATENT, REFS, 50, DEV)
-
-
-def _job(p, nb=3):
-    """Target pose p in one replay: nb camera batches, ctx / y = [uc | (uc) | c], start latent."""
-    from cd360 import synth
-    cam = synth.pose_batch(1, REFS, seed=100 + p, n_train=50)[0]
-    g = torch.Generator(device=DEV).manual_seed(7 + p)
-    ctx = torch.randn(2, 77, 2048, generator=g, device=DEV).to(BF)
-    y = torch.randn(2, 2816, generator=g, device=DEV).to(BF)
-    x = torch.randn(1, 4, LATENT, LATENT, generator=g, device=DEV)
-    return [cam] * nb, torch.cat([ctx[0:1]] * (nb - 1) + [ctx[1:2]]), torch.cat([y[0:1]] * (nb - 1) + [y[1:2]]), x
-
-
-@functools.lru_cache(maxsize=1)
 def _dpm_job():
-    """3 poses x all 4 steps of a 4-step schedule through ONE graph-mode DPM++ 2M sampler (job.sample_poses): (latents, the sampler)."""
-    from cd360 import job
-    held = {}
-
-    def make_sampler(pose, ctx, y):
-        held["smp"] = job.Sampler(_net(), pose, ctx, y, STEPS, use_graph=True, solver="dpmpp2m")
-        return held["smp"]
-
-    with torch.no_grad():
-        latents, mine = job.sample_poses(make_sampler, _job, POSES, STEPS, world=1, rank=0)
-    assert mine == list(range(POSES))
-    return latents, held["smp"]
+    """SC.walk under DPM++ 2M: (latents, the sampler)."""
+    return SC.walk(solver="dpmpp2m")
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _release_the_shared_job():
-    """The UNet and the captured sampler are built once for this file; let go of them when it is done."""
     yield
-    _dpm_job.cache_clear()
-    _net.cache_clear()
-    if torch.cuda.is_available():
-        torch.cuda.empty_cache()
+    SC.release()
 
 
 @pytest.mark.gpu
@@ -261,10 +199,10 @@ def test_dpmpp2m_job_through_two_captured_graphs():
     assert smp.mult_tab.shape == (STEPS, 4) and smp.mult_tab[-1].tolist() == [0.0, -1.0, 1.0, 0.0] and smp.gd.shape == smp.gx.shape
     assert torch.equal(smp.gd, latents[POSES - 1:]) and torch.equal(smp.gx, smp.gd)
     for p in range(POSES):
-        pose, ctx, y, x0 = _job(p)
-        fresh = job.sample_assigned(job.Sampler(_net(), pose, ctx, y, STEPS, use_graph=True, solver="dpmpp2m"), [(pose, ctx, y, x0)], STEPS)[0]
+        pose, ctx, y, x0 = SC.job(p)
+        fresh = job.sample_assigned(job.Sampler(SC.net(), pose, ctx, y, STEPS, use_graph=True, solver="dpmpp2m"), [(pose, ctx, y, x0)], STEPS)[0]
         assert torch.equal(fresh, latents[p:p + 1]), (p, float((fresh - latents[p:p + 1]).abs().max()))
-        eager = job.sample_assigned(job.Sampler(_net(), pose, ctx, y, STEPS, use_graph=False, solver="dpmpp2m"), [(pose, ctx, y, x0)], STEPS)[0]
+        eager = job.sample_assigned(job.Sampler(SC.net(), pose, ctx, y, STEPS, use_graph=False, solver="dpmpp2m"), [(pose, ctx, y, x0)], STEPS)[0]
         assert torch.equal(eager, latents[p:p + 1]), (p, float((eager - latents[p:p + 1]).abs().max()))
     assert float((latents[0] - latents[1]).abs().max() / latents[1].abs().max()) > 1e-2  # different trajectories
 
@@ -275,7 +213,7 @@ def test_captured_tail_applies_the_multistep_row_to_its_buffers():
     """One mid step of the captured graph, isolated from the UNet: with gx / gd snapshotted around the replay of step 2,
     x_after == m1 x_before - m2 (m3 gd_after - m4 gd_before) restated in torch, bit for bit (gd_after is this step's d0)."""
     _, smp = _dpm_job()
-    pose, ctx, y, x0 = _job(0)
+    pose, ctx, y, x0 = SC.job(0)
     smp.retarget(pose, ctx, y)
     x = smp.step(x0.clone(), 0, alias=True)
     x = smp.step(x, 1, alias=True)
@@ -296,16 +234,16 @@ def test_dpmpp2m_differs_from_euler_and_the_unstaged_route_serves_it():
     eager run, and not the Euler result."""
     from cd360 import job, routes
     latents, _ = _dpm_job()
-    pose, ctx, y, x0 = _job(0)
-    eul = job.sample_poses(lambda pose, ctx, y: job.Sampler(_net(), pose, ctx, y, STEPS, use_graph=True, solver="euler"), _job, POSES, STEPS)[0]
+    pose, ctx, y, x0 = SC.job(0)
+    eul = job.sample_poses(lambda pose, ctx, y: job.Sampler(SC.net(), pose, ctx, y, STEPS, use_graph=True, solver="euler"), SC.job, POSES, STEPS)[0]
     for p in range(POSES):
         d = float((eul[p] - latents[p]).abs().max() / latents[p].abs().max())
         print(f"pose {p}: Euler vs DPM++ 2M, 4 steps: rel", d)
         assert d > 1e-3, (p, d)
     with routes.override(no_stage=True):
-        g_smp = job.Sampler(_net(), pose, ctx, y, STEPS, use_graph=True, solver="dpmpp2m")
-        e_smp = job.Sampler(_net(), pose, ctx, y, STEPS, use_graph=False, solver="dpmpp2m")
-        u_eul = job.Sampler(_net(), pose, ctx, y, STEPS, use_graph=False, solver="euler")
+        g_smp = job.Sampler(SC.net(), pose, ctx, y, STEPS, use_graph=True, solver="dpmpp2m")
+        e_smp = job.Sampler(SC.net(), pose, ctx, y, STEPS, use_graph=False, solver="dpmpp2m")
+        u_eul = job.Sampler(SC.net(), pose, ctx, y, STEPS, use_graph=False, solver="euler")
         assert not g_smp.staged and not e_smp.staged
         got_g = job.sample_assigned(g_smp, [(pose, ctx, y, x0)], STEPS)[0]
         got_e = job.sample_assigned(e_smp, [(pose, ctx, y, x0)], STEPS)[0]
@@ -328,26 +266,14 @@ def test_dpmpp2m_job_agrees_with_the_uncaptured_module_route(nb):
     on this schedule).
     Measured (MI355X, one session): Euler on the parent commit 5.488e-2 of the latent's maximum for three branches (6.147e-2 for two);
     DPM++ 2M 6.085e-2 for three branches, 6.430e-2 for two; bar 1.098e-1 for both.  DESIGN.md section 6.2."""
-    from cd360 import job, sampling
+    from cd360 import job
     from cd360 import sampler as S
-    net = _net()
-    pose, ctx, y, x0 = _job(0, nb)
+    net = SC.net()
+    pose, ctx, y, x0 = SC.job(0, nb)
     got = job.sample_assigned(job.Sampler(net, pose, ctx, y, STEPS, scale_im=3.5 if nb == 3 else 0, use_graph=True, solver="dpmpp2m"),
                               [(pose, ctx, y, x0)], STEPS)[0]
-    gcfg = ({"target": "sgm.modules.diffusionmodules.guiders.VanillaCFGImgRef", "params": {"scale": 7.5}} if nb == 2 else
-            {"target": "sgm.modules.diffusionmodules.guiders.ScheduledCFGImgTextRef", "params": {"scale": 7.5, "scale_im": 3.5}})
-    mod = S.DPMPP2MSampler(num_steps=STEPS, guider_config=gcfg, device=DEV)
-    den = S.DiscreteDenoiser().to(DEV)
-    sampling.set_cfg_branches(net, nb)
-    sampling.clear_rendered_feat(net)
-    c, uc = {"crossattn": ctx[nb - 1:], "vector": y[nb - 1:]}, {"crossattn": ctx[:1], "vector": y[:1]}
-    network = lambda x_in, t, cond: (net(x_in, timesteps=t, context=cond["crossattn"], y=cond["vector"], pose=pose)[0], None, None, None)  # noqa: E731
-    sig = mod.discretization(STEPS, device=DEV)
-    x, old = x0.clone(), None
-    for i in range(STEPS):
-        x, old = mod.sampler_step(old, None if i == 0 else sig[i - 1].reshape(1), sig[i].reshape(1), sig[i + 1].reshape(1),
-                                  lambda inp, s, cond: den(network, inp, s, cond), x, c, uc)
-    sampling.clear_rendered_feat(net)
+    mod = S.DPMPP2MSampler(num_steps=STEPS, guider_config=SC.guider_config(nb), device=DEV)
+    x = SC.module_route(net, mod, "dpmpp2m", nb, pose, ctx, y, x0, STEPS)
     dev = float((got - x).abs().max() / x.abs().max())
     bar = 2 * PARENT_EULER_JOB_VS_MODULE_REL
     print(f"{nb}-branch DPM++ 2M job vs module route, 4 steps: max abs", float((got - x).abs().max()), "rel", dev, "| bar", bar)

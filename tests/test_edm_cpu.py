@@ -5,12 +5,12 @@ fourth signature table, and the job sampler's solver="heun" / s_churn.  CPU only
 job."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import sampler_cases as SC
 from test_dpmpp2m_cpu import DISC, GUIDERS, conds, row_network
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -268,16 +268,12 @@ def test_edm_header_matches_the_fourth_signature_table():
     `cd360_...(` word, comments included); the library exports the five symbols, typed; no older table holds the new names and no older
     header names them; null pointers are refused on the host (no GPU needed)."""
     from cd360 import _lib
-    header = open(os.path.join(ROOT, "include", "cd360_edm.h")).read()
-    declared = set(re.findall(r"\b(cd360_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(_lib.EDM_SIGNATURES) == set(NEW), declared ^ set(_lib.EDM_SIGNATURES)
-    assert not (set(_lib.SIGNATURES) | set(_lib.SOLVER_SIGNATURES) | set(_lib.STOCHASTIC_SIGNATURES)) & set(NEW)
-    for older in ("cd360_hip.h", "cd360_solvers.h", "cd360_stochastic.h"):
-        assert not any(n in open(os.path.join(ROOT, "include", older)).read() for n in NEW), older
-    lib = _lib.load(check_symbols=True)
-    for name in NEW:
-        fn = getattr(lib, name)
-        assert isinstance(fn, ctypes._CFuncPtr) and fn.restype is ctypes.c_int and list(fn.argtypes) == _lib.EDM_SIGNATURES[name][1]
+    older = ("cd360_hip.h", "cd360_solvers.h", "cd360_stochastic.h")
+    mismatch, in_tables, in_headers, mistyped, lib = SC.check_header_matches_table("cd360_edm.h", _lib.EDM_SIGNATURES, NEW, older)
+    assert not mismatch, mismatch
+    assert not in_tables, in_tables
+    assert not in_headers, in_headers
+    assert not mistyped, mistyped
     nul = ctypes.c_void_p(None)
     assert lib.cd360_edm_churn_f32(nul, nul, nul, nul, nul, 1, 16, nul) == -1
     assert lib.cd360_cfg_edm_predict_cl(nul, nul, nul, nul, 7.5, 3.5, nul, nul, 1, 16, 4, nul) == -1

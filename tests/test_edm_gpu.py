@@ -2,9 +2,6 @@
 predictor / corrector tails bit for bit against a torch restatement, their memory safety, the GPU trajectories against the reference's
 goldens, and the sampling job with solver="heun" and with s_churn > 0.  Needs an MI355X."""
 import functools
-import os
-import re
-import sys
 
 import numpy as np
 import pytest
@@ -12,12 +9,9 @@ import torch
 
 import guarded as G
 import philox_ref as P
+import sampler_cases as SC
+from sampler_cases import BF, DEV, LATENT, POSES, SEED, STEPS, R, seed_t, step_t, streams_t
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-DEV = "cuda"
-BF = torch.bfloat16
 NEW = ["cd360_edm_churn_f32", "cd360_cfg_edm_predict_cl", "cd360_cfg_edm_predict_f32", "cd360_cfg_edm_correct_cl", "cd360_cfg_edm_correct_f32"]
 BIG_SEED = 2 ** 63 + 12345
 ALL = dict(s_churn=40.0, s_noise=1.003)  # every row churned, clamped to sqrt 2 - 1: row 0's sigma_hat lies above the grid
@@ -29,19 +23,6 @@ C1 = dict(s_churn=1.0, s_noise=1.003)  # the golden's un-clamped setting
 # the box and in the session of this change, per branch count: three branches 5.488e-2 of the latent's maximum, two branches 6.147e-2.
 PARENT_EULER_JOB_VS_MODULE_REL = {3: 0.05488, 2: 0.06147}
 BAR_FACTOR = {"euler": 2, "heun": 4}  # churned Euler: the margin the ancestral test grants a larger step; Heun: two evaluations per step
-
-
-def seed_t(seed):
-    from cd360.sampler import seed_words
-    return torch.tensor([seed_words(seed)], dtype=torch.int64, device=DEV)
-
-
-def step_t(step):
-    return torch.tensor([step], dtype=torch.int32, device=DEV)
-
-
-def streams_t(ids):
-    return None if ids is None else torch.tensor(ids, dtype=torch.int32, device=DEV)
 
 
 @functools.lru_cache(maxsize=None)
@@ -96,20 +77,10 @@ def test_churn_kernel_adds_the_documented_noise(bs, H, Wd):
 
 
 # ================================================================================================ 7: predictor and corrector, bit for bit
-def _combine(x, e, s, scale, scale_im):
-    if scale_im is None:
-        e_u, e_c = e.chunk(2)
-        du, dc = x - s * e_u, x - s * e_c
-        return du + scale * (dc - du)
-    e_u, e_i, e_c = e.chunk(3)
-    du, dic, dc = x - s * e_u, x - s * e_i, x - s * e_c
-    return du + scale * (dc - dic) + scale_im * (dic - du)
-
-
 def _predict(x, e, row, scale, scale_im):
     """The predictor in the kernels' order, one fp32 rounding per operation (torch's elementwise kernels do not contract) -> (x_e, d)."""
     sh, sn, _, sq = row.unbind()
-    d = (x - _combine(x, e, sq, scale, scale_im)) / sh
+    d = (x - SC.combine(x, e, sq, scale, scale_im)) / sh
     return x + d * (sn - sh), d
 
 
@@ -117,12 +88,8 @@ def _correct(x, xe, d, e2, row, crow, scale, scale_im):
     sh, sn = row[0], row[1]
     if not float(sn) > 0.0:
         return xe.clone()
-    d_new = (xe - _combine(xe, e2, crow[3], scale, scale_im)) / sn
+    d_new = (xe - SC.combine(xe, e2, crow[3], scale, scale_im)) / sn
     return x + (d + d_new) / 2.0 * (sn - sh)
-
-
-def _cl_to_nchw(e16, n, H, Wd):
-    return e16[..., :4].float().reshape(n, H, Wd, 4).permute(0, 3, 1, 2).contiguous()
 
 
 ROWS = {"first-row": ("all", 0), "middle-row": ("all", 2), "last-row": ("all", 3), "unchurned-row": ("cw", 0)}
@@ -146,7 +113,7 @@ def test_predict_and_correct_equal_a_torch_restatement_in_the_kernels_order(scal
     x = torch.randn(bs, 4, H, Wd, generator=g, device=DEV)
     eps16 = torch.randn(nb * bs, H * Wd, 16, generator=g, device=DEV).to(BF)
     eps16b = torch.randn(nb * bs, H * Wd, 16, generator=g, device=DEV).to(BF)
-    e, e2 = _cl_to_nchw(eps16, nb * bs, H, Wd), _cl_to_nchw(eps16b, nb * bs, H, Wd)
+    e, e2 = SC.cl_to_nchw(eps16, nb * bs, H, Wd), SC.cl_to_nchw(eps16b, nb * bs, H, Wd)
     gi, r, cr = step_t(row), edm[row].contiguous(), corr[row].contiguous()
     assert (float(r[3]) != float(r[0])) == (case != "unchurned-row") and (float(r[1]) == 0.0) == (case == "last-row")
     want_e, want_d = _predict(x, e, r, 7.5, scale_im)
@@ -241,16 +208,6 @@ def test_host_refuses_bad_arguments():
 
 
 # ================================================================================================ 9: guarded runs
-def _guardfn(fn):
-    fn.wants_guard = True
-    return fn
-
-
-def R(*shape, seed=0, dtype=torch.float32):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    return torch.randn(*shape, generator=g, device=DEV).to(dtype)
-
-
 GUARDED = []  # (id, declares, bs, H, W, nb, tag, row): what test_every_edm_entry_point_has_a_guarded_case reads
 for _bs, _H, _W in ((1, 5, 7), (2, 24, 40)):
     for _nb in (3, 2):
@@ -275,7 +232,7 @@ def test_churn_predict_and_correct_write_their_outputs_only(declares, bs, H, Wd,
     tail = bs if nb == 2 else 0
     last, quiet = float(edm[row, 1]) == 0.0, float(churn[row, 1]) == 0.0
 
-    @_guardfn
+    @SC.guardfn
     def fn(x, e, e2, e16, e16b, edm, corr, churn, step, seed, streams, guard):
         T = guard.torch
 
@@ -315,7 +272,7 @@ def test_churn_predict_and_correct_write_their_outputs_only(declares, bs, H, Wd,
     assert torch.equal(xe, want_e) and (last or torch.equal(dv, want_d))
     assert torch.equal(xh, d["x"]) == quiet
     assert torch.equal(out, _correct(xh, xe, want_d, d["e2"], r, cr, 7.5, scale_im))
-    e_cl, e2_cl = _cl_to_nchw(d["e16"], nb * bs, H, Wd), _cl_to_nchw(d["e16b"], nb * bs, H, Wd)
+    e_cl, e2_cl = SC.cl_to_nchw(d["e16"], nb * bs, H, Wd), SC.cl_to_nchw(d["e16b"], nb * bs, H, Wd)
     cl_e, cl_d = _predict(xh, e_cl, r, 7.5, scale_im)
     assert torch.equal(gxe, cl_e) and torch.equal(gxc, _correct(xh, cl_e, cl_d, e2_cl, r, cr, 7.5, scale_im))
 
@@ -324,13 +281,10 @@ def test_every_edm_entry_point_has_a_guarded_case():
     """The twin of test_every_stochastic_entry_point_has_a_guarded_case for include/cd360_edm.h (runs without a GPU): every
     `int cd360_...(` the header declares is in some guarded case's `declares` in this file, and is typed in EDM_SIGNATURES."""
     from cd360 import _lib
-    src = open(os.path.join(ROOT, "include", "cd360_edm.h")).read()
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    names = set(re.findall(r"\b(?:int|int64_t)\s+(cd360_\w+)\s*\(", src))
-    assert names == set(_lib.EDM_SIGNATURES) and names, names ^ set(_lib.EDM_SIGNATURES)
-    declared = {e for c in GUARDED for e in c[1]}
-    assert declared <= names, declared - names
-    assert not names - declared, f"launching entry points without a guarded case: {sorted(names - declared)}"
+    untyped, unknown, uncovered = SC.check_guarded_cover("cd360_edm.h", _lib.EDM_SIGNATURES, GUARDED)
+    assert not untyped, untyped
+    assert not unknown, unknown
+    assert not uncovered, f"launching entry points without a guarded case: {sorted(uncovered)}"
 
 
 # ================================================================================================ 10: the GPU trajectories
@@ -355,58 +309,18 @@ def test_fused_steps_on_the_gpu_walk_the_reference_trajectory(name, solver, tag)
 
 
 # ================================================================================================ 11 - 13: the job
-LATENT, REFS, STEPS, POSES, SEED = 32, 6, 4, 3, 360
 JOBS = {"heun-c0": dict(solver="heun"), "heun-cw": dict(solver="heun", **CW), "euler-c1": dict(solver="euler", **C1)}
 
 
-@functools.lru_cache(maxsize=1)
-def _net():
-    import bench
-    return bench.build_model(LATENT, REFS, 50, DEV)
-
-
-def _job(p, nb=3):
-    """Target pose p in one replay: nb camera batches, ctx / y = [uc | (uc) | c], start latent."""
-    from cd360 import synth
-    cam = synth.pose_batch(1, REFS, seed=100 + p, n_train=50)[0]
-    g = torch.Generator(device=DEV).manual_seed(7 + p)
-    ctx = torch.randn(2, 77, 2048, generator=g, device=DEV).to(BF)
-    y = torch.randn(2, 2816, generator=g, device=DEV).to(BF)
-    x = torch.randn(1, 4, LATENT, LATENT, generator=g, device=DEV)
-    return [cam] * nb, torch.cat([ctx[0:1]] * (nb - 1) + [ctx[1:2]]), torch.cat([y[0:1]] * (nb - 1) + [y[1:2]]), x
-
-
-def _sampler(pose, ctx, y, n_steps=STEPS, **kw):
-    from cd360 import job
-    kw = dict(dict(use_graph=True, seed=SEED), **kw)
-    return job.Sampler(_net(), pose, ctx, y, n_steps, **kw)
-
-
-@functools.lru_cache(maxsize=None)
 def _edm_job(which):
-    """3 poses x all 4 steps of a 4-step schedule through ONE graph-mode sampler (job.sample_poses): (latents, the sampler).
-    which = a key of JOBS, or "euler": the plain solver the others are told apart from."""
-    from cd360 import job
-    held = {}
-
-    def make_sampler(pose, ctx, y):
-        held["smp"] = _sampler(pose, ctx, y, **JOBS.get(which, {}))
-        return held["smp"]
-
-    with torch.no_grad():
-        latents, mine = job.sample_poses(make_sampler, _job, POSES, STEPS, world=1, rank=0)
-    assert mine == list(range(POSES))
-    return latents, held["smp"]
+    """SC.walk for a key of JOBS, or for "euler": the plain solver the others are told apart from."""
+    return SC.walk(**JOBS.get(which, {}))
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _release_the_shared_job():
-    """The UNet and the captured samplers are built once for this file; let go of them when it is done."""
     yield
-    _edm_job.cache_clear()
-    _net.cache_clear()
-    if torch.cuda.is_available():
-        torch.cuda.empty_cache()
+    SC.release()
 
 
 @pytest.mark.gpu
@@ -437,12 +351,12 @@ def test_edm_job_through_its_captured_graphs(which):
         assert smp.churned and smp.seed_buf.tolist() == [SEED] and smp.streams_buf.tolist() == [0]
         assert (smp.churn_tab[:, 1] > 0).tolist() == ([False, True, True, True] if which == "heun-cw" else [True] * 4)
     for p in range(POSES):
-        pose, ctx, y, x0 = _job(p)
-        fresh = job.sample_assigned(_sampler(pose, ctx, y, **kw), [(pose, ctx, y, x0)], STEPS)[0]
+        pose, ctx, y, x0 = SC.job(p)
+        fresh = job.sample_assigned(SC.sampler(pose, ctx, y, **kw), [(pose, ctx, y, x0)], STEPS)[0]
         assert torch.equal(fresh, latents[p:p + 1]), (p, float((fresh - latents[p:p + 1]).abs().max()))
-        eager = job.sample_assigned(_sampler(pose, ctx, y, use_graph=False, **kw), [(pose, ctx, y, x0)], STEPS)[0]
+        eager = job.sample_assigned(SC.sampler(pose, ctx, y, use_graph=False, **kw), [(pose, ctx, y, x0)], STEPS)[0]
         assert torch.equal(eager, latents[p:p + 1]), (p, float((eager - latents[p:p + 1]).abs().max()))
-    pose, ctx, y, x0 = _job(0)
+    pose, ctx, y, x0 = SC.job(0)
     smp.retarget(pose, ctx, y)
     x1 = smp.step(x0.clone(), 0)
     for i in (1, 2, 3):  # step i twice from the same x: the same bits
@@ -462,10 +376,10 @@ def test_edm_job_through_its_captured_graphs(which):
 def test_one_step_heun_is_one_step_euler():
     """n_steps = 1: the only step is the sigma_next = 0 row, Heun's corrector is skipped and the predictor on the EDM tables must hold the
     Euler step's bits -- graph mode (Heun launches this step un-captured) and eager."""
-    pose, ctx, y, x0 = _job(0)
+    pose, ctx, y, x0 = SC.job(0)
     for use_graph in (True, False):
-        h = _sampler(pose, ctx, y, n_steps=1, solver="heun", use_graph=use_graph)
-        e = _sampler(pose, ctx, y, n_steps=1, solver="euler", use_graph=use_graph)
+        h = SC.sampler(pose, ctx, y, n_steps=1, solver="heun", use_graph=use_graph)
+        e = SC.sampler(pose, ctx, y, n_steps=1, solver="euler", use_graph=use_graph)
         a, b = h.step(x0.clone(), 0), e.step(x0.clone(), 0)
         assert torch.isfinite(a).all() and torch.equal(a, b), float((a - b).abs().max())
         assert torch.equal(h.edm_tab[0, :3], e.step_tab[0, :3])
@@ -476,12 +390,12 @@ def test_one_step_heun_is_one_step_euler():
 def test_unstaged_route_serves_heun_and_churn():
     """With routes.no_stage the un-staged route carries both: finite, graph mode equal to its own eager run, and not the Euler result."""
     from cd360 import job, routes
-    pose, ctx, y, x0 = _job(0)
+    pose, ctx, y, x0 = SC.job(0)
     with routes.override(no_stage=True):
-        u_eul = job.sample_assigned(_sampler(pose, ctx, y, use_graph=False, solver="euler"), [(pose, ctx, y, x0)], STEPS)[0]
+        u_eul = job.sample_assigned(SC.sampler(pose, ctx, y, use_graph=False, solver="euler"), [(pose, ctx, y, x0)], STEPS)[0]
         for which in ("heun-cw", "euler-c1"):
-            g_smp = _sampler(pose, ctx, y, **JOBS[which])
-            e_smp = _sampler(pose, ctx, y, use_graph=False, **JOBS[which])
+            g_smp = SC.sampler(pose, ctx, y, **JOBS[which])
+            e_smp = SC.sampler(pose, ctx, y, use_graph=False, **JOBS[which])
             assert not g_smp.staged and not e_smp.staged
             got_g = job.sample_assigned(g_smp, [(pose, ctx, y, x0)], STEPS)[0]
             got_e = job.sample_assigned(e_smp, [(pose, ctx, y, x0)], STEPS)[0]
@@ -498,7 +412,7 @@ def test_captured_churn_follows_seed_and_streams():
     windowed setting, under Heun's render graph -- the two seeds give bit-equal x.  (The noise passes through the UNet here: the
     difference term itself is held at the kernel level, test_churn_kernel_adds_the_documented_noise.)"""
     _, smp = _edm_job("euler-c1")
-    pose, ctx, y, x0 = _job(0)
+    pose, ctx, y, x0 = SC.job(0)
     smp.retarget(pose, ctx, y)
     snap = smp.step(x0.clone(), 0)
     graph, res = smp.graph, {}
@@ -541,27 +455,15 @@ def test_edm_job_agrees_with_the_uncaptured_module_route(nb, which):
     Bar: what the SAME comparison gives under plain EULER on the parent commit at the same branch count, measured on the same box in the
     same session (tools/solver_report.py), times 2 for churned Euler (the margin the ancestral test grants a larger step) and times 4 for
     Heun (two evaluations per step, each contributing that rounding).  Measured figures: DESIGN.md section 6.3."""
-    from cd360 import job, sampling
+    from cd360 import job
     from cd360 import sampler as S
     kw = dict(JOBS[which])
     solver = kw.pop("solver")
-    net = _net()
-    pose, ctx, y, x0 = _job(0, nb)
-    got = job.sample_assigned(_sampler(pose, ctx, y, scale_im=3.5 if nb == 3 else 0, solver=solver, **kw), [(pose, ctx, y, x0)], STEPS)[0]
-    gcfg = ({"target": "sgm.modules.diffusionmodules.guiders.VanillaCFGImgRef", "params": {"scale": 7.5}} if nb == 2 else
-            {"target": "sgm.modules.diffusionmodules.guiders.ScheduledCFGImgTextRef", "params": {"scale": 7.5, "scale_im": 3.5}})
-    mod = (S.HeunEDMSampler if solver == "heun" else S.EulerEDMSampler)(num_steps=STEPS, guider_config=gcfg, device=DEV, seed=SEED, **kw)
-    den = S.DiscreteDenoiser().to(DEV)
-    sampling.set_cfg_branches(net, nb)
-    sampling.clear_rendered_feat(net)
-    c, uc = {"crossattn": ctx[nb - 1:], "vector": y[nb - 1:]}, {"crossattn": ctx[:1], "vector": y[:1]}
-    network = lambda x_in, t, cond: (net(x_in, timesteps=t, context=cond["crossattn"], y=cond["vector"], pose=pose)[0], None, None, None)  # noqa: E731
-    sig = mod.discretization(STEPS, device=DEV)
-    x = x0.clone()
-    for i in range(STEPS):
-        x, _ = mod.sampler_step(sig[i].reshape(1), sig[i + 1].reshape(1), lambda inp, s, cond: den(network, inp, s, cond), x, c, uc,
-                                mod.gamma_of(sig[i], STEPS))
-    sampling.clear_rendered_feat(net)
+    net = SC.net()
+    pose, ctx, y, x0 = SC.job(0, nb)
+    got = job.sample_assigned(SC.sampler(pose, ctx, y, scale_im=3.5 if nb == 3 else 0, solver=solver, **kw), [(pose, ctx, y, x0)], STEPS)[0]
+    mod = (S.HeunEDMSampler if solver == "heun" else S.EulerEDMSampler)(num_steps=STEPS, guider_config=SC.guider_config(nb), device=DEV, seed=SEED, **kw)
+    x = SC.module_route(net, mod, solver, nb, pose, ctx, y, x0, STEPS)
     dev = float((got - x).abs().max() / x.abs().max())
     bar = BAR_FACTOR[solver] * PARENT_EULER_JOB_VS_MODULE_REL[nb]
     print(f"{which} {nb}-branch job vs module route, 4 steps: max abs", float((got - x).abs().max()), "rel", dev, "| bar", bar)

@@ -5,12 +5,12 @@ of the device noise (tests/philox_ref.py): known answers and statistics.  CPU on
 captured job."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import sampler_cases as SC
 import philox_ref as P
 from test_dpmpp2m_cpu import DISC, GUIDERS, conds, row_network
 
@@ -200,16 +200,12 @@ def test_stochastic_header_matches_the_third_signature_table():
     cd360_hip.h to (every `cd360_...(` word, comments included); the library exports the three symbols, typed; neither older table holds
     the new names and neither older header names them; null pointers are refused on the host (no GPU needed)."""
     from cd360 import _lib
-    header = open(os.path.join(ROOT, "include", "cd360_stochastic.h")).read()
-    declared = set(re.findall(r"\b(cd360_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(_lib.STOCHASTIC_SIGNATURES) == set(NEW), declared ^ set(_lib.STOCHASTIC_SIGNATURES)
-    assert not (set(_lib.SIGNATURES) | set(_lib.SOLVER_SIGNATURES)) & set(NEW)
-    for older in ("cd360_hip.h", "cd360_solvers.h"):
-        assert not any(n in open(os.path.join(ROOT, "include", older)).read() for n in NEW), older
-    lib = _lib.load(check_symbols=True)
-    for name in NEW:
-        fn = getattr(lib, name)
-        assert isinstance(fn, ctypes._CFuncPtr) and fn.restype is ctypes.c_int and list(fn.argtypes) == _lib.STOCHASTIC_SIGNATURES[name][1]
+    older = ("cd360_hip.h", "cd360_solvers.h")
+    mismatch, in_tables, in_headers, mistyped, lib = SC.check_header_matches_table("cd360_stochastic.h", _lib.STOCHASTIC_SIGNATURES, NEW, older)
+    assert not mismatch, mismatch
+    assert not in_tables, in_tables
+    assert not in_headers, in_headers
+    assert not mistyped, mistyped
     nul = ctypes.c_void_p(None)
     assert lib.cd360_sampler_noise_f32(nul, nul, nul, nul, 1, 16, nul) == -1
     assert lib.cd360_cfg_euler_ancestral_step_f32(nul, nul, nul, nul, nul, nul, nul, 7.5, 3.5, nul, 1, 16, nul) == -1

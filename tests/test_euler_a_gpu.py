@@ -2,9 +2,6 @@
 ancestral Euler tails bit for bit against a torch restatement, their memory safety, the GPU trajectory against the reference's golden,
 and the sampling job with solver="euler_a".  Needs an MI355X."""
 import functools
-import os
-import re
-import sys
 
 import numpy as np
 import pytest
@@ -12,12 +9,9 @@ import torch
 
 import guarded as G
 import philox_ref as P
+import sampler_cases as SC
+from sampler_cases import BF, DEV, LATENT, POSES, SEED, STEPS, R, seed_t, step_t, streams_t
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-DEV = "cuda"
-BF = torch.bfloat16
 NEW = ["cd360_sampler_noise_f32", "cd360_cfg_euler_ancestral_step_f32", "cd360_cfg_euler_ancestral_step_cl"]
 BIG_SEED = 2 ** 63 + 12345
 
@@ -26,19 +20,6 @@ BIG_SEED = 2 ** 63 + 12345
 # and in the session of this change: three branches 5.488e-2 of the latent's maximum (max |difference| 1.468 of 26.76), two branches
 # 6.147e-2 (1.680 of 27.34).  The bar of BOTH branch counts is twice the smaller, three-branch figure.
 PARENT_EULER_JOB_VS_MODULE_REL = 0.05488
-
-
-def seed_t(seed):
-    from cd360.sampler import seed_words
-    return torch.tensor([seed_words(seed)], dtype=torch.int64, device=DEV)
-
-
-def step_t(step):
-    return torch.tensor([step], dtype=torch.int32, device=DEV)
-
-
-def streams_t(ids):
-    return None if ids is None else torch.tensor(ids, dtype=torch.int32, device=DEV)
 
 
 # ================================================================================================ 1: the noise kernel
@@ -99,14 +80,7 @@ def test_noise_kernel_statistics():
 def _restated(x, e, s, anc, z, scale, scale_im):
     """The kernels' expression in the kernels' order, one fp32 rounding per operation (torch's elementwise kernels do not contract) ->
     (x_e, x')."""
-    if scale_im is None:
-        e_u, e_c = e.chunk(2)
-        du, dc = x - s * e_u, x - s * e_c
-        d0 = du + scale * (dc - du)
-    else:
-        e_u, e_i, e_c = e.chunk(3)
-        du, dic, dc = x - s * e_u, x - s * e_i, x - s * e_c
-        d0 = du + scale * (dc - dic) + scale_im * (dic - du)
+    d0 = SC.combine(x, e, s, scale, scale_im)
     sd, su, s_noise, _ = anc.unbind()
     xe = x + (x - d0) / s * (sd - s)
     return xe, (xe if float(su) == 0.0 else xe + (z * s_noise) * su)
@@ -209,16 +183,6 @@ def test_host_refuses_bad_arguments():
 
 
 # ================================================================================================ 4: guarded runs
-def _guardfn(fn):
-    fn.wants_guard = True
-    return fn
-
-
-def R(*shape, seed=0, dtype=torch.float32):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    return torch.randn(*shape, generator=g, device=DEV).to(dtype)
-
-
 GUARDED = []  # (id, declares, bs, H, W, nb, row): what test_every_stochastic_entry_point_has_a_guarded_case reads
 for _bs, _H, _W in ((1, 5, 7), (2, 24, 40)):
     for _nb in (3, 2):
@@ -239,7 +203,7 @@ def test_noise_and_tails_write_their_outputs_only(declares, bs, H, Wd, nb, row):
              step=step_t(row), seed=seed_t(BIG_SEED), streams=streams_t(list(range(1, bs + 1))))
     tail = bs if nb == 2 else 0
 
-    @_guardfn
+    @SC.guardfn
     def fn(x, e, e16, tab, anc, step, seed, streams, guard):
         ge = guard.torch.empty((nb * bs + tail, 4, H, Wd), dtype=torch.float32, device=DEV)
         ge[:nb * bs].copy_(e)
@@ -268,13 +232,10 @@ def test_every_stochastic_entry_point_has_a_guarded_case():
     """The twin of test_every_solver_entry_point_has_a_guarded_case for include/cd360_stochastic.h (runs without a GPU): every
     `int cd360_...(` the header declares is in some guarded case's `declares` in this file, and is typed in STOCHASTIC_SIGNATURES."""
     from cd360 import _lib
-    src = open(os.path.join(ROOT, "include", "cd360_stochastic.h")).read()
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    names = set(re.findall(r"\b(?:int|int64_t)\s+(cd360_\w+)\s*\(", src))
-    assert names == set(_lib.STOCHASTIC_SIGNATURES) and names, names ^ set(_lib.STOCHASTIC_SIGNATURES)
-    declared = {e for c in GUARDED for e in c[1]}
-    assert declared <= names, declared - names
-    assert not names - declared, f"launching entry points without a guarded case: {sorted(names - declared)}"
+    untyped, unknown, uncovered = SC.check_guarded_cover("cd360_stochastic.h", _lib.STOCHASTIC_SIGNATURES, GUARDED)
+    assert not untyped, untyped
+    assert not unknown, unknown
+    assert not uncovered, f"launching entry points without a guarded case: {sorted(uncovered)}"
 
 
 # ================================================================================================ 5: the GPU trajectory
@@ -299,56 +260,18 @@ def test_fused_step_on_the_gpu_walks_the_reference_trajectory(name, tag):
 
 
 # ================================================================================================ 6 - 8: the job
-LATENT, REFS, STEPS, POSES, SEED = 32, 6, 4, 3, 360
+_sampler = functools.partial(SC.sampler, solver="euler_a")
 
 
-@functools.lru_cache(maxsize=1)
-def _net():
-    import bench
-    return bench.build_model(LATENT, REFS, 50, DEV)
-
-
-def _job(p, nb=3):
-    """Target pose p in one replay: nb camera batches, ctx / y = [uc | (uc) | c], start latent."""
-    from cd360 import synth
-    cam = synth.pose_batch(1, REFS, seed=100 + p, n_train=50)[0]
-    g = torch.Generator(device=DEV).manual_seed(7 + p)
-    ctx = torch.randn(2, 77, 2048, generator=g, device=DEV).to(BF)
-    y = torch.randn(2, 2816, generator=g, device=DEV).to(BF)
-    x = torch.randn(1, 4, LATENT, LATENT, generator=g, device=DEV)
-    return [cam] * nb, torch.cat([ctx[0:1]] * (nb - 1) + [ctx[1:2]]), torch.cat([y[0:1]] * (nb - 1) + [y[1:2]]), x
-
-
-def _sampler(pose, ctx, y, **kw):
-    from cd360 import job
-    kw = dict(dict(use_graph=True, solver="euler_a", seed=SEED), **kw)
-    return job.Sampler(_net(), pose, ctx, y, STEPS, **kw)
-
-
-@functools.lru_cache(maxsize=1)
 def _anc_job():
-    """3 poses x all 4 steps of a 4-step schedule through ONE graph-mode ancestral sampler (job.sample_poses): (latents, the sampler)."""
-    from cd360 import job
-    held = {}
-
-    def make_sampler(pose, ctx, y):
-        held["smp"] = _sampler(pose, ctx, y)
-        return held["smp"]
-
-    with torch.no_grad():
-        latents, mine = job.sample_poses(make_sampler, _job, POSES, STEPS, world=1, rank=0)
-    assert mine == list(range(POSES))
-    return latents, held["smp"]
+    """SC.walk under ancestral Euler: (latents, the sampler)."""
+    return SC.walk(solver="euler_a")
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _release_the_shared_job():
-    """The UNet and the captured sampler are built once for this file; let go of them when it is done."""
     yield
-    _anc_job.cache_clear()
-    _net.cache_clear()
-    if torch.cuda.is_available():
-        torch.cuda.empty_cache()
+    SC.release()
 
 
 @pytest.mark.gpu
@@ -364,13 +287,13 @@ def test_euler_a_job_through_two_captured_graphs():
     assert smp.anc_tab.shape == (STEPS, 4) and smp.anc_tab[-1].tolist() == [0.0, 0.0, 1.0, 0.0] and bool((smp.anc_tab[:-1, 1] > 0).all())
     assert smp.seed_buf.dtype == torch.int64 and smp.seed_buf.tolist() == [SEED] and smp.streams_buf.tolist() == [0]
     for p in range(POSES):
-        pose, ctx, y, x0 = _job(p)
+        pose, ctx, y, x0 = SC.job(p)
         fresh = job.sample_assigned(_sampler(pose, ctx, y), [(pose, ctx, y, x0)], STEPS)[0]
         assert torch.equal(fresh, latents[p:p + 1]), (p, float((fresh - latents[p:p + 1]).abs().max()))
         eager = job.sample_assigned(_sampler(pose, ctx, y, use_graph=False), [(pose, ctx, y, x0)], STEPS)[0]
         assert torch.equal(eager, latents[p:p + 1]), (p, float((eager - latents[p:p + 1]).abs().max()))
     assert float((latents[0] - latents[1]).abs().max() / latents[1].abs().max()) > 1e-2  # different trajectories
-    pose, ctx, y, x0 = _job(0)
+    pose, ctx, y, x0 = SC.job(0)
     smp.retarget(pose, ctx, y)
     x1 = smp.step(x0.clone(), 0)
     for i in (1, 2):  # step i twice from the same x: the same bits
@@ -387,7 +310,7 @@ def test_captured_tail_adds_the_documented_noise():
     roundings of magnitude <= max |x| per side).  set_noise_streams changes the result; on the last step the two seeds give bit-equal x."""
     from cd360 import ops
     _, smp = _anc_job()
-    pose, ctx, y, x0 = _job(0)
+    pose, ctx, y, x0 = SC.job(0)
     smp.retarget(pose, ctx, y)
     snap = smp.step(x0.clone(), 0)
     graph = smp.graph
@@ -423,8 +346,8 @@ def test_euler_a_differs_from_euler_and_the_unstaged_route_serves_it():
     the un-staged route carries ancestral Euler as well: finite, graph mode equal to its own eager run, and not the Euler result."""
     from cd360 import job, routes
     latents, _ = _anc_job()
-    pose, ctx, y, x0 = _job(0)
-    eul = job.sample_poses(lambda pose, ctx, y: _sampler(pose, ctx, y, solver="euler"), _job, POSES, STEPS)[0]
+    pose, ctx, y, x0 = SC.job(0)
+    eul = job.sample_poses(lambda pose, ctx, y: _sampler(pose, ctx, y, solver="euler"), SC.job, POSES, STEPS)[0]
     for p in range(POSES):
         d = float((eul[p] - latents[p]).abs().max() / latents[p].abs().max())
         print(f"pose {p}: Euler vs ancestral Euler, 4 steps: rel", d)
@@ -453,24 +376,13 @@ def test_euler_a_job_agrees_with_the_uncaptured_module_route(nb):
     |sigma_down - sigma| step widens the gap, by less than a factor of two on this schedule.
     Bar: twice what the SAME comparison gives under EULER on the parent commit (three branches), measured on the same box in the same
     session (tools/solver_report.py).  Measured figures: DESIGN.md section 6.3."""
-    from cd360 import job, sampling
+    from cd360 import job
     from cd360 import sampler as S
-    net = _net()
-    pose, ctx, y, x0 = _job(0, nb)
+    net = SC.net()
+    pose, ctx, y, x0 = SC.job(0, nb)
     got = job.sample_assigned(_sampler(pose, ctx, y, scale_im=3.5 if nb == 3 else 0), [(pose, ctx, y, x0)], STEPS)[0]
-    gcfg = ({"target": "sgm.modules.diffusionmodules.guiders.VanillaCFGImgRef", "params": {"scale": 7.5}} if nb == 2 else
-            {"target": "sgm.modules.diffusionmodules.guiders.ScheduledCFGImgTextRef", "params": {"scale": 7.5, "scale_im": 3.5}})
-    mod = S.EulerAncestralSampler(num_steps=STEPS, guider_config=gcfg, device=DEV, seed=SEED)
-    den = S.DiscreteDenoiser().to(DEV)
-    sampling.set_cfg_branches(net, nb)
-    sampling.clear_rendered_feat(net)
-    c, uc = {"crossattn": ctx[nb - 1:], "vector": y[nb - 1:]}, {"crossattn": ctx[:1], "vector": y[:1]}
-    network = lambda x_in, t, cond: (net(x_in, timesteps=t, context=cond["crossattn"], y=cond["vector"], pose=pose)[0], None, None, None)  # noqa: E731
-    sig = mod.discretization(STEPS, device=DEV)
-    x = x0.clone()
-    for i in range(STEPS):
-        x = mod.sampler_step(sig[i].reshape(1), sig[i + 1].reshape(1), lambda inp, s, cond: den(network, inp, s, cond), x, c, uc)
-    sampling.clear_rendered_feat(net)
+    mod = S.EulerAncestralSampler(num_steps=STEPS, guider_config=SC.guider_config(nb), device=DEV, seed=SEED)
+    x = SC.module_route(net, mod, "euler_a", nb, pose, ctx, y, x0, STEPS)
     dev = float((got - x).abs().max() / x.abs().max())
     bar = 2 * PARENT_EULER_JOB_VS_MODULE_REL
     print(f"{nb}-branch ancestral job vs module route, 4 steps: max abs", float((got - x).abs().max()), "rel", dev, "| bar", bar)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import sampler_cases as SC
 from test_dpmpp2m_cpu import DISC, GUIDERS, conds, row_network
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -320,16 +321,12 @@ def test_highorder_header_matches_the_fifth_signature_table():
     (every `cd360_...(` word, comments included); the library exports the six symbols, typed; no older table holds the new names and no
     older header names them; null pointers are refused on the host (no GPU needed)."""
     from cd360 import _lib
-    header = open(os.path.join(ROOT, "include", "cd360_highorder.h")).read()
-    declared = set(re.findall(r"\b(cd360_[a-z0-9_]+)\s*\(", header))
-    assert declared == set(_lib.HIGHORDER_SIGNATURES) == set(NEW), declared ^ set(_lib.HIGHORDER_SIGNATURES)
-    assert not (set(_lib.SIGNATURES) | set(_lib.SOLVER_SIGNATURES) | set(_lib.STOCHASTIC_SIGNATURES) | set(_lib.EDM_SIGNATURES)) & set(NEW)
-    for older in ("cd360_hip.h", "cd360_solvers.h", "cd360_stochastic.h", "cd360_edm.h"):
-        assert not any(n in open(os.path.join(ROOT, "include", older)).read() for n in NEW), older
-    lib = _lib.load(check_symbols=True)
-    for name in NEW:
-        fn = getattr(lib, name)
-        assert isinstance(fn, ctypes._CFuncPtr) and fn.restype is ctypes.c_int and list(fn.argtypes) == _lib.HIGHORDER_SIGNATURES[name][1]
+    older = ("cd360_hip.h", "cd360_solvers.h", "cd360_stochastic.h", "cd360_edm.h")
+    mismatch, in_tables, in_headers, mistyped, lib = SC.check_header_matches_table("cd360_highorder.h", _lib.HIGHORDER_SIGNATURES, NEW, older)
+    assert not mismatch, mismatch
+    assert not in_tables, in_tables
+    assert not in_headers, in_headers
+    assert not mistyped, mistyped
     nul = ctypes.c_void_p(None)
     assert lib.cd360_cfg_dpmpp2s_mid_cl(nul, nul, nul, nul, nul, 7.5, 3.5, nul, 1, 16, 4, nul) == -1
     assert lib.cd360_cfg_dpmpp2s_mid_f32(nul, nul, nul, nul, 7.5, 3.5, nul, 16, nul) == -1

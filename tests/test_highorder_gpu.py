@@ -2,9 +2,6 @@
 restatement, the noise term against the float64 restatement of the device noise (tests/philox_ref.py), host refusals, memory safety, the
 GPU trajectories against the reference's goldens, and the sampling job with solver="dpmpp2s_a" and solver="lms".  Needs an MI355X."""
 import functools
-import os
-import re
-import sys
 
 import numpy as np
 import pytest
@@ -12,12 +9,9 @@ import torch
 
 import guarded as G
 import philox_ref as P
+import sampler_cases as SC
+from sampler_cases import BF, DEV, LATENT, POSES, SEED, STEPS, R, seed_t, step_t, streams_t
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-DEV = "cuda"
-BF = torch.bfloat16
 NEW = ["cd360_cfg_dpmpp2s_mid_cl", "cd360_cfg_dpmpp2s_mid_f32", "cd360_cfg_dpmpp2s_step_cl", "cd360_cfg_dpmpp2s_step_f32", "cd360_cfg_lms_step_cl",
        "cd360_cfg_lms_step_f32"]
 BIG_SEED = 2 ** 63 + 12345
@@ -30,24 +24,6 @@ SCALE_IMS = [3.5, 0.0, -1.25, None]
 # branches 6.147e-2.
 PARENT_EULER_JOB_VS_MODULE_REL = {3: 0.05488, 2: 0.06147}
 BAR_FACTOR = {"lms": 2, "dpmpp2s_a": 4}  # one evaluation per step, as DPM++ 2M is granted; two evaluations per step, as Heun is granted
-
-
-def seed_t(seed):
-    from cd360.sampler import seed_words
-    return torch.tensor([seed_words(seed)], dtype=torch.int64, device=DEV)
-
-
-def step_t(step):
-    return torch.tensor([step], dtype=torch.int32, device=DEV)
-
-
-def streams_t(ids):
-    return None if ids is None else torch.tensor(ids, dtype=torch.int32, device=DEV)
-
-
-def R(*shape, seed=0, dtype=torch.float32):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    return torch.randn(*shape, generator=g, device=DEV).to(dtype)
 
 
 @functools.lru_cache(maxsize=None)
@@ -69,47 +45,25 @@ def _lms_tables(order, steps=6):
 
 
 # ================================================================================================ 6: the kernels, bit for bit
-def _combine(x, e, s, scale, scale_im):
-    if scale_im is None:
-        e_u, e_c = e.chunk(2)
-        du, dc = x - s * e_u, x - s * e_c
-        return du + scale * (dc - du)
-    e_u, e_i, e_c = e.chunk(3)
-    du, dic, dc = x - s * e_u, x - s * e_i, x - s * e_c
-    return du + scale * (dc - dic) + scale_im * (dic - du)
-
-
 def _mid(x, e, s, mult, scale, scale_im):
     """The midpoint in the kernels' order, one fp32 rounding per operation (torch's elementwise kernels do not contract)."""
-    return mult[0] * x - mult[1] * _combine(x, e, s, scale, scale_im)
+    return mult[0] * x - mult[1] * SC.combine(x, e, s, scale, scale_im)
 
 
 def _step2s(x, x2, e2, midrow, mult, anc, z, scale, scale_im):
-    xn = mult[2] * x - mult[3] * _combine(x2, e2, midrow[3], scale, scale_im)
+    xn = mult[2] * x - mult[3] * SC.combine(x2, e2, midrow[3], scale, scale_im)
     return xn if float(anc[1]) == 0.0 else xn + (z * anc[2]) * anc[1]
 
 
 def _lms(x, e, ring, s, coef, i, scale, scale_im):
     """-> x'; ring [order, ...] updated in place, slot i % order"""
     order = ring.shape[0]
-    d = (x - _combine(x, e, s, scale, scale_im)) / s
+    d = (x - SC.combine(x, e, s, scale, scale_im)) / s
     ring[i % order] = d
     acc = coef[0] * d
     for j in range(1, min(i + 1, order)):
         acc = acc + coef[j] * ring[(i - j) % order]
     return x + acc
-
-
-def _cl_to_nchw(e16, n, H, Wd):
-    return e16[..., :4].float().reshape(n, H, Wd, 4).permute(0, 3, 1, 2).contiguous()
-
-
-def _eps_forms(nb, bs, H, Wd, seed):
-    """Two channels-last eps of the SAME values: ld = 4 (rows of their own) and ld = 8 (channels 0..3 of 8-wide rows); and their NCHW fp32."""
-    e8 = R(nb * bs, H * Wd, 8, seed=seed, dtype=BF)
-    e4 = e8[..., :4].contiguous()
-    assert e4.stride(1) == 4 and e8[..., :4].stride(1) == 8
-    return (e4, e8[..., :4]), _cl_to_nchw(e8, nb * bs, H, Wd)
 
 
 ROWS = {"first-row": (1.0, 0), "middle-row": (1.0, 2), "last-row": (1.0, 3), "single-row": (1.5, 1)}  # (eta, row of the 4-step schedule)
@@ -127,7 +81,7 @@ def test_dpmpp2s_kernels_equal_a_torch_restatement_in_the_kernels_order(scale_im
     from cd360 import ops
     nb = 2 if scale_im is None else 3
     x = R(bs, 4, H, Wd, seed=11)
-    (cl_forms, e), (cl2_forms, e2) = _eps_forms(nb, bs, H, Wd, 12), _eps_forms(nb, bs, H, Wd, 13)
+    (cl_forms, e), (cl2_forms, e2) = SC.eps_forms(nb, bs, H, Wd, 12), SC.eps_forms(nb, bs, H, Wd, 13)
     seed, streams = seed_t(BIG_SEED), streams_t(list(range(3, 3 + bs)))
     for case, (eta, row) in ROWS.items():
         tab, anc, mid, mult = _tables(eta)
@@ -177,7 +131,7 @@ def test_lms_kernels_equal_a_torch_restatement_in_the_kernels_order(scale_im, bs
     wrapped = False
     for i in range(6):
         x = R(bs, 4, H, Wd, seed=20 + i)
-        cl_forms, e = _eps_forms(nb, bs, H, Wd, 40 + i)
+        cl_forms, e = SC.eps_forms(nb, bs, H, Wd, 40 + i)
         s, coef, gi = tab[i, 0:1].contiguous(), lms[i].contiguous(), step_t(i)
         before = ring_ref.clone()
         want = _lms(x, e, ring_ref, s, coef, i, 7.5, scale_im)
@@ -309,11 +263,6 @@ def test_host_refuses_bad_arguments():
 
 
 # ================================================================================================ 9: guarded runs
-def _guardfn(fn):
-    fn.wants_guard = True
-    return fn
-
-
 GUARDED = []  # (id, declares, bs, H, W, nb, eta, row): what test_every_highorder_entry_point_has_a_guarded_case reads
 for _bs, _H, _W in SHAPES:
     for _nb in (3, 2):
@@ -338,7 +287,7 @@ def test_highorder_tails_write_their_outputs_only(declares, bs, H, Wd, nb, eta, 
              step=step_t(row), step3=step_t(row + 3), seed=seed_t(BIG_SEED), streams=streams_t(list(range(1, bs + 1))))
     tail = bs if nb == 2 else 0
 
-    @_guardfn
+    @SC.guardfn
     def fn(x, e, e2, e16, e16b, hist, tab, anc, mid, mult, ltab, lms, step, step3, seed, streams, guard):
         T = guard.torch
 
@@ -382,7 +331,7 @@ def test_highorder_tails_write_their_outputs_only(declares, bs, H, Wd, nb, eta, 
 
     (x2, gx2, out, gxs, res), _ = G.run_twice(fn, d, declares=declares)
     x, s, a, m, mu = d["x"], tab[row, 0:1], anc[row], mid[row], mult[row]
-    e_cl, e2_cl = _cl_to_nchw(d["e16"], nb * bs, H, Wd), _cl_to_nchw(d["e16b"], nb * bs, H, Wd)
+    e_cl, e2_cl = SC.cl_to_nchw(d["e16"], nb * bs, H, Wd), SC.cl_to_nchw(d["e16b"], nb * bs, H, Wd)
     z = ops.sampler_noise(d["seed"], d["streams"], d["step"], bs, H, Wd)
     assert torch.equal(x2, _mid(x, d["e"], s, mu, 7.5, scale_im)) and torch.equal(gx2, _mid(x, e_cl, s, mu, 7.5, scale_im))
     assert torch.equal(out, _step2s(x, x2, d["e2"], m, mu, a, z, 7.5, scale_im))
@@ -400,13 +349,10 @@ def test_every_highorder_entry_point_has_a_guarded_case():
     """The twin of test_every_edm_entry_point_has_a_guarded_case for include/cd360_highorder.h (runs without a GPU): every `int cd360_...(`
     the header declares is in some guarded case's `declares` in this file, and is typed in HIGHORDER_SIGNATURES."""
     from cd360 import _lib
-    src = open(os.path.join(ROOT, "include", "cd360_highorder.h")).read()
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    names = set(re.findall(r"\b(?:int|int64_t)\s+(cd360_\w+)\s*\(", src))
-    assert names == set(_lib.HIGHORDER_SIGNATURES) and names, names ^ set(_lib.HIGHORDER_SIGNATURES)
-    declared = {e for c in GUARDED for e in c[1]}
-    assert declared <= names, declared - names
-    assert not names - declared, f"launching entry points without a guarded case: {sorted(names - declared)}"
+    untyped, unknown, uncovered = SC.check_guarded_cover("cd360_highorder.h", _lib.HIGHORDER_SIGNATURES, GUARDED)
+    assert not untyped, untyped
+    assert not unknown, unknown
+    assert not uncovered, f"launching entry points without a guarded case: {sorted(uncovered)}"
 
 
 # ================================================================================================ 10: the GPU trajectories
@@ -431,58 +377,18 @@ def test_fused_steps_on_the_gpu_walk_the_reference_trajectory(name, solver, tag)
 
 
 # ================================================================================================ 11 - 13: the job
-LATENT, REFS, STEPS, POSES, SEED = 32, 6, 4, 3, 360
 JOBS = {"dpmpp2s_a": dict(solver="dpmpp2s_a", eta=1.0), "lms": dict(solver="lms", order=3)}  # order 3: the ring wraps at step 3
 
 
-@functools.lru_cache(maxsize=1)
-def _net():
-    import bench
-    return bench.build_model(LATENT, REFS, 50, DEV)
-
-
-def _job(p, nb=3):
-    """Target pose p in one replay: nb camera batches, ctx / y = [uc | (uc) | c], start latent."""
-    from cd360 import synth
-    cam = synth.pose_batch(1, REFS, seed=100 + p, n_train=50)[0]
-    g = torch.Generator(device=DEV).manual_seed(7 + p)
-    ctx = torch.randn(2, 77, 2048, generator=g, device=DEV).to(BF)
-    y = torch.randn(2, 2816, generator=g, device=DEV).to(BF)
-    x = torch.randn(1, 4, LATENT, LATENT, generator=g, device=DEV)
-    return [cam] * nb, torch.cat([ctx[0:1]] * (nb - 1) + [ctx[1:2]]), torch.cat([y[0:1]] * (nb - 1) + [y[1:2]]), x
-
-
-def _sampler(pose, ctx, y, n_steps=STEPS, **kw):
-    from cd360 import job
-    kw = dict(dict(use_graph=True, seed=SEED), **kw)
-    return job.Sampler(_net(), pose, ctx, y, n_steps, **kw)
-
-
-@functools.lru_cache(maxsize=None)
 def _ho_job(which):
-    """3 poses x all 4 steps of a 4-step schedule through ONE graph-mode sampler (job.sample_poses): (latents, the sampler).
-    which = a key of JOBS, or "euler": the plain solver the others are told apart from."""
-    from cd360 import job
-    held = {}
-
-    def make_sampler(pose, ctx, y):
-        held["smp"] = _sampler(pose, ctx, y, **JOBS.get(which, {}))
-        return held["smp"]
-
-    with torch.no_grad():
-        latents, mine = job.sample_poses(make_sampler, _job, POSES, STEPS, world=1, rank=0)
-    assert mine == list(range(POSES))
-    return latents, held["smp"]
+    """SC.walk for a key of JOBS, or for "euler": the plain solver the others are told apart from."""
+    return SC.walk(**JOBS.get(which, {}))
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _release_the_shared_job():
-    """The UNet and the captured samplers are built once for this file; let go of them when it is done."""
     yield
-    _ho_job.cache_clear()
-    _net.cache_clear()
-    if torch.cuda.is_available():
-        torch.cuda.empty_cache()
+    SC.release()
 
 
 @pytest.mark.gpu
@@ -509,12 +415,12 @@ def test_highorder_job_through_its_captured_graphs(which):
         assert smp.lgraph is None and smp.gds.shape == (3,) + tuple(smp.gx.shape) and smp.lms_tab.shape == (STEPS, 4) and smp.order == 3
         assert bool((smp.lms_tab[3, :3] != 0).all()) and float(smp.lms_tab[3, 3]) == 0.0
     for p in range(POSES):
-        pose, ctx, y, x0 = _job(p)
-        fresh = job.sample_assigned(_sampler(pose, ctx, y, **kw), [(pose, ctx, y, x0)], STEPS)[0]
+        pose, ctx, y, x0 = SC.job(p)
+        fresh = job.sample_assigned(SC.sampler(pose, ctx, y, **kw), [(pose, ctx, y, x0)], STEPS)[0]
         assert torch.equal(fresh, latents[p:p + 1]), (p, float((fresh - latents[p:p + 1]).abs().max()))
-        eager = job.sample_assigned(_sampler(pose, ctx, y, use_graph=False, **kw), [(pose, ctx, y, x0)], STEPS)[0]
+        eager = job.sample_assigned(SC.sampler(pose, ctx, y, use_graph=False, **kw), [(pose, ctx, y, x0)], STEPS)[0]
         assert torch.equal(eager, latents[p:p + 1]), (p, float((eager - latents[p:p + 1]).abs().max()))
-    pose, ctx, y, x0 = _job(0)
+    pose, ctx, y, x0 = SC.job(0)
     smp.retarget(pose, ctx, y)
     x1 = smp.step(x0.clone(), 0)
     for i in (1, 2, 3):  # step i twice from the same x: the same bits (the ring's slot i % order is rewritten with the same direction)
@@ -534,10 +440,10 @@ def test_highorder_job_through_its_captured_graphs(which):
 def test_one_step_dpmpp2s_is_one_step_euler_ancestral():
     """n_steps = 1: the only step is the sigma_down = 0 row, DPM++ 2S takes one evaluation and must hold the ancestral Euler step's bits at
     the same seed and eta -- graph mode (this step is launched un-captured) and eager."""
-    pose, ctx, y, x0 = _job(0)
+    pose, ctx, y, x0 = SC.job(0)
     for use_graph in (True, False):
-        s2 = _sampler(pose, ctx, y, n_steps=1, solver="dpmpp2s_a", eta=1.0, use_graph=use_graph)
-        ea = _sampler(pose, ctx, y, n_steps=1, solver="euler_a", eta=1.0, use_graph=use_graph)
+        s2 = SC.sampler(pose, ctx, y, n_steps=1, solver="dpmpp2s_a", eta=1.0, use_graph=use_graph)
+        ea = SC.sampler(pose, ctx, y, n_steps=1, solver="euler_a", eta=1.0, use_graph=use_graph)
         a, b = s2.step(x0.clone(), 0), ea.step(x0.clone(), 0)
         assert torch.isfinite(a).all() and torch.equal(a, b), float((a - b).abs().max())
         assert s2.single_rows == [True] and s2.graph is None and torch.equal(s2.anc_tab, ea.anc_tab)
@@ -550,12 +456,12 @@ def test_interior_single_rows_run_on_the_one_evaluation_graph():
     through the captured sampler -- row 0 renders un-captured, the other single rows replay the one-evaluation graph -- equals the eager
     run bit for bit, and is finite."""
     from cd360 import job
-    pose, ctx, y, x0 = _job(0)
-    g_smp = _sampler(pose, ctx, y, n_steps=12, solver="dpmpp2s_a", eta=1.5)
+    pose, ctx, y, x0 = SC.job(0)
+    g_smp = SC.sampler(pose, ctx, y, n_steps=12, solver="dpmpp2s_a", eta=1.5)
     got = job.sample_assigned(g_smp, [(pose, ctx, y, x0)], 12)[0]
     assert g_smp.single_rows == [i in (0, 1, 2, 3, 4, 8, 9, 10, 11) for i in range(12)]
     assert g_smp.graph is not None and g_smp.lgraph is not None and g_smp.rgraph is None and torch.isfinite(got).all()
-    eager = job.sample_assigned(_sampler(pose, ctx, y, n_steps=12, solver="dpmpp2s_a", eta=1.5, use_graph=False), [(pose, ctx, y, x0)], 12)[0]
+    eager = job.sample_assigned(SC.sampler(pose, ctx, y, n_steps=12, solver="dpmpp2s_a", eta=1.5, use_graph=False), [(pose, ctx, y, x0)], 12)[0]
     assert torch.equal(got, eager), float((got - eager).abs().max())
 
 
@@ -566,7 +472,7 @@ def test_captured_dpmpp2s_follows_seed_and_streams():
     restores the bits; set_noise_streams changes the result and restoring it restores the bits.  On the last step (sigma_up = 0) the two
     seeds give bit-equal x.  (The difference term itself is held at the kernel level, test_dpmpp2s_step_adds_the_documented_noise.)"""
     _, smp = _ho_job("dpmpp2s_a")
-    pose, ctx, y, x0 = _job(0)
+    pose, ctx, y, x0 = SC.job(0)
     smp.retarget(pose, ctx, y)
     snap = smp.step(x0.clone(), 0)
     graph, res = smp.graph, {}
@@ -593,12 +499,12 @@ def test_captured_dpmpp2s_follows_seed_and_streams():
 def test_unstaged_route_serves_both_solvers():
     """With routes.no_stage the un-staged route carries both: finite, graph mode equal to its own eager run, and not the Euler result."""
     from cd360 import job, routes
-    pose, ctx, y, x0 = _job(0)
+    pose, ctx, y, x0 = SC.job(0)
     with routes.override(no_stage=True):
-        u_eul = job.sample_assigned(_sampler(pose, ctx, y, use_graph=False, solver="euler"), [(pose, ctx, y, x0)], STEPS)[0]
+        u_eul = job.sample_assigned(SC.sampler(pose, ctx, y, use_graph=False, solver="euler"), [(pose, ctx, y, x0)], STEPS)[0]
         for which in JOBS:
-            g_smp = _sampler(pose, ctx, y, **JOBS[which])
-            e_smp = _sampler(pose, ctx, y, use_graph=False, **JOBS[which])
+            g_smp = SC.sampler(pose, ctx, y, **JOBS[which])
+            e_smp = SC.sampler(pose, ctx, y, use_graph=False, **JOBS[which])
             assert not g_smp.staged and not e_smp.staged
             got_g = job.sample_assigned(g_smp, [(pose, ctx, y, x0)], STEPS)[0]
             got_e = job.sample_assigned(e_smp, [(pose, ctx, y, x0)], STEPS)[0]
@@ -608,33 +514,15 @@ def test_unstaged_route_serves_both_solvers():
 
 
 def module_route(net, which, nb, pose, ctx, y, x0, steps=STEPS):
-    """The un-captured module route: cd360.sampler's class + the guider + DiscreteDenoiser around the same UNet, eager."""
+    """SC.module_route under this file's class for JOBS[which]."""
     from cd360 import sampler as S
-    from cd360 import sampling
-    gcfg = ({"target": "sgm.modules.diffusionmodules.guiders.VanillaCFGImgRef", "params": {"scale": 7.5}} if nb == 2 else
-            {"target": "sgm.modules.diffusionmodules.guiders.ScheduledCFGImgTextRef", "params": {"scale": 7.5, "scale_im": 3.5}})
     kw = dict(JOBS[which])
     kw.pop("solver")
-    den = S.DiscreteDenoiser().to(DEV)
-    sampling.set_cfg_branches(net, nb)
-    sampling.clear_rendered_feat(net)
-    c, uc = {"crossattn": ctx[nb - 1:], "vector": y[nb - 1:]}, {"crossattn": ctx[:1], "vector": y[:1]}
-    network = lambda x_in, t, cond: (net(x_in, timesteps=t, context=cond["crossattn"], y=cond["vector"], pose=pose)[0], None, None, None)  # noqa: E731
-    denoiser = lambda inp, s, cond: den(network, inp, s, cond)  # noqa: E731
     if which == "dpmpp2s_a":
-        mod = S.DPMPP2SAncestralSampler(num_steps=steps, guider_config=gcfg, device=DEV, seed=SEED, **kw)
+        mod = S.DPMPP2SAncestralSampler(num_steps=steps, guider_config=SC.guider_config(nb), device=DEV, seed=SEED, **kw)
     else:
-        mod = S.LinearMultistepSampler(num_steps=steps, guider_config=gcfg, device=DEV, **kw)
-    sig = mod.discretization(steps, device=DEV)
-    x, ds = x0.clone(), []
-    table = S.lms_coefficients(sig, kw["order"]) if which == "lms" else None
-    for i in range(steps):
-        if which == "dpmpp2s_a":
-            x = mod.sampler_step(sig[i].reshape(1), sig[i + 1].reshape(1), denoiser, x, c, uc)
-        else:
-            x = mod.sampler_step(ds, [float(table[i, j]) for j in range(min(i + 1, mod.order))], sig[i].reshape(1), denoiser, x, c, uc)
-    sampling.clear_rendered_feat(net)
-    return x
+        mod = S.LinearMultistepSampler(num_steps=steps, guider_config=SC.guider_config(nb), device=DEV, **kw)
+    return SC.module_route(net, mod, which, nb, pose, ctx, y, x0, steps, order=kw.get("order"))
 
 
 @pytest.mark.gpu
@@ -651,9 +539,9 @@ def test_highorder_job_agrees_with_the_uncaptured_module_route(nb, which):
     same session (tools/solver_report.py), times 2 for the linear multistep solver (one evaluation per step, as DPM++ 2M is granted) and
     times 4 for DPM++ 2S (two evaluations per step, as Heun is granted).  Measured figures: DESIGN.md section 6.4."""
     from cd360 import job
-    net = _net()
-    pose, ctx, y, x0 = _job(0, nb)
-    got = job.sample_assigned(_sampler(pose, ctx, y, scale_im=3.5 if nb == 3 else 0, **JOBS[which]), [(pose, ctx, y, x0)], STEPS)[0]
+    net = SC.net()
+    pose, ctx, y, x0 = SC.job(0, nb)
+    got = job.sample_assigned(SC.sampler(pose, ctx, y, scale_im=3.5 if nb == 3 else 0, **JOBS[which]), [(pose, ctx, y, x0)], STEPS)[0]
     x = module_route(net, which, nb, pose, ctx, y, x0)
     dev = float((got - x).abs().max() / x.abs().max())
     bar = BAR_FACTOR[which] * PARENT_EULER_JOB_VS_MODULE_REL[nb]

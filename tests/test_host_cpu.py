@@ -274,6 +274,19 @@ def test_library_exports_every_declared_symbol():
     assert lib.cd360_conv_stats_slabs(320) == 4 and lib.cd360_conv_stats_slabs(640) == 2 and lib.cd360_conv_k_order(1280, 9) == 5
 
 
+def test_every_header_is_bound_by_exactly_one_signature_table():
+    """cd360._lib.ABI names every header under include/ and nothing else; the functions each header declares outside comments are the
+    keys of its table, one for one; no name is typed twice.  A header added without a table, or a table load() never binds, fails here."""
+    import sampler_cases as SC
+    from cd360 import _lib
+    assert list(_lib.ABI) and set(_lib.ABI) == {f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h")}
+    for header, table in _lib.ABI.items():
+        declared = SC.declared_functions(header)
+        assert declared == set(table), (header, declared ^ set(table))
+    names = [n for table in _lib.ABI.values() for n in table]
+    assert len(names) == len(set(names)), sorted(n for n in set(names) if names.count(n) > 1)
+
+
 def test_gemm_dispatch_contract_of_the_sdxl_shapes():
     """The host side sizes two buffers from what the GEMM dispatcher will choose (no GPU needed to ask): the row-statistics partials of a
     residual-stream GEMM (one per `cd360_gemm_tile_n` columns, consumed by the next LayerNorm fold) and the 64- or 32-row channel
