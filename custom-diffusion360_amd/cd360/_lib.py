@@ -1,5 +1,5 @@
 """ctypes binding of libcd360_hip.so (the C ABI declared in include/cd360_hip.h, include/cd360_solvers.h,
-include/cd360_stochastic.h, include/cd360_edm.h and include/cd360_highorder.h).
+include/cd360_stochastic.h, include/cd360_edm.h, include/cd360_highorder.h and include/cd360_image.h).
 
 There is NO fallback: if the shared library is missing or a symbol is absent this module raises.
 The library is built in-tree by `__graft_entry__.build()` (hipcc --offload-arch=gfx950)."""
@@ -144,9 +144,17 @@ HIGHORDER_SIGNATURES = {
     "cd360_cfg_lms_step_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_float, c_int, _P, c_int64, _P]),
 }
 
+# include/cd360_image.h: the start latent, the first stage's posterior sample, the decoder's front end and its uint8 image output.
+IMAGE_SIGNATURES = {
+    "cd360_start_noise_f32": (c_int, [_P, _P, _P, _P, c_int, c_int64, _P]),
+    "cd360_posterior_sample_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, _P, c_int, c_int64, _P]),
+    "cd360_post_quant_f32": (c_int, [_P, _P, _P, c_float, _P, c_int, c_int64, _P]),
+    "cd360_vae_conv_out_u8": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+}
+
 # the whole C ABI: header under include/ -> its table, in the order the headers were added.  load() binds and symbol-checks every entry.
 ABI = {"cd360_hip.h": SIGNATURES, "cd360_solvers.h": SOLVER_SIGNATURES, "cd360_stochastic.h": STOCHASTIC_SIGNATURES,
-       "cd360_edm.h": EDM_SIGNATURES, "cd360_highorder.h": HIGHORDER_SIGNATURES}
+       "cd360_edm.h": EDM_SIGNATURES, "cd360_highorder.h": HIGHORDER_SIGNATURES, "cd360_image.h": IMAGE_SIGNATURES}
 
 TUNING_FIELDS = ("gemm_cfg", "gemm_group_m", "gemm_movers", "gemm_ksplit", "conv_cfg", "conv_dma", "conv_kgroup", "conv_wide", "conv_wmajor",
                  "conv_split", "attn_smallk", "attn_smallk_wgs", "attn_self", "attn_fast", "nerf_kernel", "qattn_cfg", "whatif", "gemm_small", "qattn_keys16",

@@ -6,6 +6,8 @@ uc)` with the patched UNet, `clear_rendered_feat` between images).  Here every r
 it, samples those poses with ONE `Sampler` -- whose render step and steady-state step are each captured once into a hipGraph and re-pointed
 at the next pose by `Sampler.retarget` (camera buffer and conditioning rewritten in place) -- and the ranks exchange nothing until
 `shard.gather_latents` collects the final latents (RCCL all-gather over xGMI; gloo in the CPU tests).  `bench.py` times exactly this loop.
+`sample_images` is the same job from a seed to uint8 images: the start latent drawn on the device (`start_latent`), every rank decoding its
+own poses through the first stage (cd360/images.py), and the one all-gather moving the images instead of the latents.
 """
 from __future__ import annotations
 
@@ -405,3 +407,44 @@ def sample_poses(make_sampler: Callable, make_job: Callable[[int], tuple], num_p
     sampler = make_sampler(*jobs[0][:3])
     finals = sample_assigned(sampler, jobs, steps)
     return shard.gather_latents(torch.cat(finals, 0), num_poses), mine
+
+
+@torch.no_grad()
+def start_latent(sampler, H: int, W: int, seed: int, streams=None) -> torch.Tensor:
+    """The start latent of a trajectory, [bs, 4, H, W] fp32 on the sampler's device: what `torch.randn` (sample.py:290-292) and
+    `x *= torch.sqrt(1.0 + sigmas[0] ** 2.0)` (sampling.py:50) give the reference, drawn by cd360_start_noise_f32 as a pure function of
+    (`seed`, the row's stream id, channel, pixel) -- not of torch's generator state, and unrelated to the noise a stochastic solver injects
+    under the same seed (another domain of the counter, include/cd360_image.h).  `streams`: one id per row (default: stream 0 everywhere,
+    every row the same latent).  Serves every solver: it reads `sampler.sigmas` / `sampler.bs` and none of the sampler's noise state."""
+    from cd360 import ops
+    from cd360.sampler import seed_words
+    sig = sampler.sigmas
+    bs = int(getattr(sampler, "bs", 1))
+    if streams is not None and len(streams) != bs:
+        raise ValueError(f"{len(streams)} noise stream ids for {bs} replay rows")
+    scale = torch.sqrt(1.0 + sig[0] ** 2.0).float().reshape(1)  # sampling.py:50, by torch on the schedule's own sigma_0
+    seed_t = torch.tensor([seed_words(seed)], dtype=torch.int64, device=sig.device)
+    streams_t = None if streams is None else torch.tensor([int(v) for v in streams], dtype=torch.int32, device=sig.device)
+    return ops.start_noise(seed_t, streams_t, scale, bs, H, W)
+
+
+def sample_images(make_sampler: Callable, make_job: Callable[[int], tuple], num_poses: int, steps: int, first_stage, world: int = 1, rank: int = 0,
+                  seed: int = 0, latent_hw=None):
+    """Poses and a seed in, images out: `sample_poses` with the first stage on every rank.  `make_job(p)` builds pose p's (pose, ctx, y, x0);
+    where x0 is None the pose starts from `start_latent(sampler, *latent_hw, seed)` -- stream 0, so all poses share their start noise as in
+    sample.py:290-292 -- and `latent_hw` = (H, W) of the latent must be given.  Each rank decodes ITS poses with `first_stage.decode_u8`
+    (cd360/images.py::FirstStage, or anything with that method); the one collective is an all-gather of the uint8 images.  Returns (images
+    [num_poses, H, W, 3] uint8 in pose order, identical on every rank and for every `world`; this rank's pose indices)."""
+    if num_poses < world:  # decided from the arguments alone, so EVERY rank raises (see sample_poses)
+        raise ValueError("more ranks than target poses: every rank needs at least one pose (the all-gather is sized per rank)")
+    mine = shard.assign_poses(num_poses, world, rank)
+    jobs = [make_job(p) for p in mine]
+    sampler = make_sampler(*jobs[0][:3])
+    if any(j[3] is None for j in jobs):
+        if latent_hw is None:
+            raise ValueError("make_job returned x0 = None: sample_images needs latent_hw = (H, W) to draw the start latent")
+        x0 = start_latent(sampler, int(latent_hw[0]), int(latent_hw[1]), seed)
+        jobs = [(pose, ctx, y, x0 if x is None else x) for pose, ctx, y, x in jobs]
+    finals = sample_assigned(sampler, jobs, steps)
+    images = torch.cat([first_stage.decode_u8(x) for x in finals], 0)
+    return shard.gather_latents(images, num_poses), mine

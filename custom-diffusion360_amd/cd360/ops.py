@@ -1686,6 +1686,115 @@ def vae_enc_conv_out(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[tor
     return out
 
 
+# ----------------------------------------------------------------------------------------------- sampler <-> first stage (include/cd360_image.h)
+# These four refuse a bad argument with ValueError BEFORE the device check and before the library is loaded, so a refusal is the same on a
+# machine without a GPU (tests/test_images_cpu.py); a CPU tensor that passes them raises Cd360Error in _need_gpu, as everywhere above.
+def _refuse(bad: bool, what: str) -> None:
+    if bad:
+        raise ValueError(what)
+
+
+def _f32_tensor(t: torch.Tensor, shape, name: str) -> None:
+    _refuse(not isinstance(t, torch.Tensor) or t.dtype != torch.float32, f"{name}: an fp32 tensor is needed, got {getattr(t, 'dtype', type(t))}")
+    _refuse(tuple(t.shape) != tuple(shape) or not t.is_contiguous(), f"{name}: a contiguous tensor of shape {tuple(shape)} is needed, got {tuple(t.shape)}")
+
+
+def _seed_args(seed: torch.Tensor, streams: Optional[torch.Tensor], rows: int) -> None:
+    _refuse(seed.dtype != torch.int64 or seed.numel() != 1, f"seed: a 1-element int64 tensor is needed, got {seed.dtype} x {seed.numel()}")
+    _refuse(streams is not None and (streams.dtype != torch.int32 or streams.numel() != rows or not streams.is_contiguous()),
+            f"streams: None or a contiguous int32 tensor of {rows} ids is needed")
+
+
+def _overlaps(a: torch.Tensor, b: torch.Tensor) -> bool:
+    pa, pb = a.data_ptr(), b.data_ptr()
+    return pa < pb + b.numel() * b.element_size() and pb < pa + a.numel() * a.element_size()
+
+
+def _out_arg(out: Optional[torch.Tensor], shape, dtype, like: torch.Tensor, name: str) -> torch.Tensor:
+    """The result buffer: the caller's `out` (checked: dtype, shape, contiguous, not overlapping `like`) or a fresh one beside `like`."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    _refuse(out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous(),
+            f"out: a contiguous {dtype} tensor of shape {tuple(shape)} is needed, got {out.dtype} {tuple(out.shape)}")
+    _refuse(out.device != like.device, f"out is on {out.device}, {name} on {like.device}")
+    _refuse(_overlaps(out, like), f"out overlaps {name}")
+    return out
+
+
+def start_noise(seed: torch.Tensor, streams: Optional[torch.Tensor], scale: torch.Tensor, bs: int, H: int, W: int) -> torch.Tensor:
+    """The start latent of a trajectory, [bs, 4, H, W] fp32 = z * scale (cd360_start_noise_f32, include/cd360_image.h): z = the noise of
+    sampler_noise in counter domain 1 (step word 0), a pure function of (seed, streams[row], channel, pixel).  seed: device int64[1];
+    streams: device int32[bs] or None (stream 0 for every row); scale: a 1-element fp32 device tensor, sqrt(1 + sigma_0^2)."""
+    _refuse(bs <= 0 or H <= 0 or W <= 0, f"bs, H, W must be positive, got {bs}, {H}, {W}")
+    _seed_args(seed, streams, bs)
+    _refuse(scale.dtype != torch.float32 or scale.numel() != 1, f"scale: a 1-element fp32 tensor is needed, got {scale.dtype} x {scale.numel()}")
+    _need_gpu(seed, streams, scale)
+    out = torch.empty((bs, 4, H, W), dtype=torch.float32, device=seed.device)
+    check(_lib.load().cd360_start_noise_f32(_ptr(out), _ptr(seed), _ptr(streams), _ptr(scale), bs, H * W, _stream()), "cd360_start_noise_f32")
+    return out
+
+
+def posterior_sample(moments: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, seed: Optional[torch.Tensor], streams: Optional[torch.Tensor],
+                     draw: Optional[torch.Tensor], scale_factor: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """quant_conv + DiagonalGaussianDistribution.sample() + scale_factor * z in one kernel (cd360_posterior_sample_f32): moments [B, 8, H, W]
+    fp32 (Encoder.forward's output), w [8, 8] / bias [8] fp32 = quant_conv's weight (output, input) and bias -> [B, 4, H, W] fp32 =
+    (mean + exp(0.5 clamp(logvar, -30, 20)) z) * scale_factor, z in counter domain 2 at (pixel, draw, streams[b]).  seed: device int64[1],
+    draw: device int32[1], streams: device int32[B] or None.  seed=None is mode(): mean * scale_factor, streams / draw ignored."""
+    _refuse(moments.ndim != 4 or moments.shape[1] != 8, f"moments: [B, 8, H, W] is needed (z_channels = 4, double_z), got {tuple(moments.shape)}")
+    B, _, H, W = moments.shape
+    _refuse(B <= 0 or H * W <= 0, f"moments is empty: {tuple(moments.shape)}")
+    _f32_tensor(moments, moments.shape, "moments")
+    _f32_tensor(w, (8, 8), "w")
+    _f32_tensor(bias, (8,), "bias")
+    if seed is not None:
+        _seed_args(seed, streams, B)
+        _refuse(draw is None or draw.dtype != torch.int32 or draw.numel() != 1, "draw: a 1-element int32 tensor is needed with a seed")
+    else:
+        streams = draw = None
+    out = _out_arg(out, (B, 4, H, W), torch.float32, moments, "moments")
+    _need_gpu(moments, w, bias, seed, streams, draw, out)
+    with _timed("posterior_sample", 2.0 * B * H * W * 72, 4.0 * B * H * W * 12):
+        check(_lib.load().cd360_posterior_sample_f32(_ptr(moments), _ptr(w), _ptr(bias), _ptr(seed), _ptr(streams), _ptr(draw), float(scale_factor),
+                                                    _ptr(out), B, H * W, _stream()), "cd360_posterior_sample_f32")
+    return out
+
+
+def post_quant(z: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, inv_scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """1 / scale_factor * z + post_quant_conv in one kernel (cd360_post_quant_f32): z [B, 4, H, W] fp32, w [4, 4] / bias [4] fp32 = the 1 x 1
+    convolution's weight (output, input) and bias -> [B, 4, H, W] fp32, the Decoder's input."""
+    _refuse(z.ndim != 4 or z.shape[1] != 4, f"z: [B, 4, H, W] is needed, got {tuple(z.shape)}")
+    B, _, H, W = z.shape
+    _refuse(B <= 0 or H * W <= 0, f"z is empty: {tuple(z.shape)}")
+    _f32_tensor(z, z.shape, "z")
+    _f32_tensor(w, (4, 4), "w")
+    _f32_tensor(bias, (4,), "bias")
+    out = _out_arg(out, z.shape, torch.float32, z, "z")
+    _need_gpu(z, w, bias, out)
+    with _timed("post_quant", 2.0 * B * H * W * 20, 4.0 * B * H * W * 8):
+        check(_lib.load().cd360_post_quant_f32(_ptr(z), _ptr(w), _ptr(bias), float(inv_scale), _ptr(out), B, H * W, _stream()), "cd360_post_quant_f32")
+    return out
+
+
+def vae_conv_out_u8(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], N: int, H: int, W: int, cout: int,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Decoder.conv_out with the image epilogue (cd360_vae_conv_out_u8): x, w_packed, bias as for vae_conv_out -> uint8 [N, H, W, cout]
+    (channels last) = (clip(v * 0.5 + 0.5, 0, 1) * 255).to(uint8) of the fp32 value v vae_conv_out writes, bit for bit; a NaN writes 0."""
+    _refuse(not 1 <= cout <= 4, f"cout = {cout}: the output convolution serves 1..4 channels")
+    _refuse(N <= 0 or H <= 0 or W <= 0, f"N, H, W must be positive, got {N}, {H}, {W}")
+    _refuse(x.dtype != torch.bfloat16 or not x.is_contiguous(), f"x: a contiguous bf16 tensor is needed, got {x.dtype}")
+    cin = x.shape[-1]
+    _refuse(x.numel() != N * H * W * cin or cin % 64 != 0, f"x: [{N}, {H * W}, Cin % 64 == 0] is needed, got {tuple(x.shape)}")
+    _f32_tensor(w_packed, (9, cin, 4), "w_packed")
+    _refuse(bias is not None and (bias.dtype != torch.float32 or bias.numel() != cout or not bias.is_contiguous()),
+            f"bias: None or {cout} contiguous fp32 values are needed")
+    out = _out_arg(out, (N, H, W, cout), torch.uint8, x, "x")
+    _need_gpu(x, w_packed, bias, out)
+    with _timed("vae_conv_out_u8", 2.0 * N * H * W * 9 * cin * cout, 2.0 * N * H * W * cin + 1.0 * N * H * W * cout):
+        check(_lib.load().cd360_vae_conv_out_u8(_ptr(x), _ptr(w_packed), _ptr(bias), _ptr(out), N, H, W, cin, cout, _stream()),
+              "cd360_vae_conv_out_u8")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- rank-r adapters (add_lora=True)
 LOWRANK_RANKS = (8, 16, 32, 64)
 _DROPOUT_STATE = {}  # device -> int64 [2] (seed, offset) read by the mask of cd360_lowrank_add_bf16 / cd360_dropout_apply_bf16

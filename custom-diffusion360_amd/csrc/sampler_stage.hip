@@ -11,6 +11,7 @@
 // pow / sqrt / reciprocal / arange / exp / sin / cos / cat / silu / casts / the 4 -> 64 channel pad of the input convolution).
 // The input convolution is computed ONCE per diffusion sample and written to its three CFG branches (their inputs are identical).
 #include "cd360_common.h"
+#include "cd360_philox.h"
 
 #include <cmath>
 #include <type_traits>
@@ -231,41 +232,12 @@ __global__ __launch_bounds__(256) void cfg_dpmpp2m_step_kernel(const float* __re
 }
 
 // ---- device noise + ancestral Euler (sampling.py:236-273, 340-347: AncestralSampler / EulerAncestralSampler.sampler_step) --------------------
-// Standard normals as a PURE FUNCTION of (seed, noise stream, step index, channel, pixel): Philox4x32-10 as published in Random123 (key = the
-// two halves of the seed, counter = (pixel, step, stream id, 0): the last word is a reserved domain tag), then Box-Muller on the four output
-// words.  One Philox call serves the four latent channels of a pixel.  Nothing here depends on the grid, on bs or on where a row sits in the
-// batch, so a graph replay, an eager launch, a fresh sampler and the un-staged route draw the same bits (include/cd360_stochastic.h).
-// Precise logf / sinf / cosf / sqrtf: the float64 restatement in tests/philox_ref.py is the yardstick.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t r[4]) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  r[0] = c0, r[1] = c1, r[2] = c2, r[3] = c3;
-}
-
-__device__ __forceinline__ void box_muller(uint32_t ra, uint32_t rb, float& za, float& zb) {
-  const float u1 = (float)((ra >> 8) + 1u) * 0x1p-24f;  // (0, 1]: exact in fp32
-  const float u2 = (float)(rb >> 8) * 0x1p-24f;         // [0, 1)
-  const float rad = sqrtf(-2.f * logf(u1));
-  const float ang = 6.2831855f * u2;
-  za = rad * cosf(ang);
-  zb = rad * sinf(ang);
-}
+// The generator itself (Philox4x32-10 + Box-Muller, counter = (pixel, step, stream id, domain)) is cd360_philox.h, shared with
+// image_stage.hip.  A step's noise is domain 0 (include/cd360_stochastic.h).
 
 // z[c] = the noise of channel c of pixel px in noise stream `strm` at step `step`
 __device__ __forceinline__ void sampler_noise4(uint32_t px, uint32_t step, uint32_t strm, uint32_t k0, uint32_t k1, float z[4]) {
-  uint32_t r[4];
-  philox4x32_10(px, step, strm, 0u, k0, k1, r);
-  box_muller(r[0], r[1], z[0], z[1]);
-  box_muller(r[2], r[3], z[2], z[3]);
+  noise4(px, step, strm, CD360_NOISE_STEP, k0, k1, z);
 }
 
 // out [bs, 4, HW] fp32; seed: device int64 read as (low, high) 32-bit words; streams [bs] int32 or null (stream 0 for every row)
@@ -641,12 +613,6 @@ inline void launch_for_branches(float scale_im, Launch&& launch) {
 // rows), 8-byte aligned for the u32x2 loads
 inline bool cl_args_ok(const void* x, const void* eps, const void* step_tab, const void* step, int bs, int64_t HW, int ld) {
   return x && eps && step_tab && step && bs > 0 && HW > 0 && ld >= 4 && ld % 4 == 0 && (uintptr_t)eps % 8 == 0;
-}
-
-// what every user of the generator asks: seed a device int64, step / streams device int32 (streams may be null), HW <= 2^32: the pixel is
-// one 32-bit counter word
-inline bool noise_args_ok(const void* seed, const void* streams, const void* step, int64_t HW) {
-  return seed && step && (uintptr_t)seed % 8 == 0 && ((uintptr_t)step | (uintptr_t)streams) % 4 == 0 && HW <= ((int64_t)1 << 32);
 }
 
 }  // namespace

@@ -14,6 +14,7 @@
 //                            split over the threads of a workgroup (16 pixels per workgroup: a 64^2 latent is 256 workgroups).
 // (The Encoder's Downsample is the register-staged convolution kernel with its tap centre moved: conv_igemm.hip.)
 #include "cd360_common.h"
+#include "vae_conv_out.h"
 
 namespace {
 
@@ -217,44 +218,16 @@ __global__ __launch_bounds__(512) void vae_conv_in_kernel(const float* __restric
   }
 }
 
-constexpr int CO_CHUNK = 256;  // input channels whose weights sit in the LDS at a time
-
 // x [B][H W][Cin] bf16; w [9][Cin][4] fp32 (tap 3 ky + kx, channel, output channel; columns >= Cout zero); out [B][Cout][H][W] fp32.
-// Grid (ceil(H W / 256), B); thread = one output pixel, all Cout <= 4 channels.
+// Grid (ceil(H W / 256), B); thread = one output pixel, all Cout <= 4 channels.  The accumulation is vae_conv_out.h's, shared with the
+// uint8 epilogue of image_stage.hip.
 __global__ __launch_bounds__(256) void vae_conv_out_kernel(const uint16_t* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ bias, float* __restrict__ out, int H, int W, int Cin, int Cout) {
   __shared__ __attribute__((aligned(16))) float wl[9 * CO_CHUNK * 4];
   const int b = blockIdx.y;
   const long HW = (long)H * W, p = (long)blockIdx.x * 256 + threadIdx.x;
   const bool live = p < HW;
-  const int y = live ? (int)(p / W) : 0, xq = live ? (int)(p - (long)y * W) : 0;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int c0 = 0; c0 < Cin; c0 += CO_CHUNK) {
-    const int cn = min(CO_CHUNK, Cin - c0);
-    __syncthreads();
-    for (int i = threadIdx.x; i < 9 * cn; i += 256) {
-      const int tap = i / cn, ci = i - tap * cn;
-      *reinterpret_cast<f32x4*>(wl + (tap * CO_CHUNK + ci) * 4) = *reinterpret_cast<const f32x4*>(w + ((long)tap * Cin + c0 + ci) * 4);
-    }
-    __syncthreads();
-    if (!live) continue;
-    for (int tap = 0; tap < 9; ++tap) {
-      const int yy = y + tap / 3 - 1, xx = xq + tap % 3 - 1;
-      if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
-      const uint16_t* xp = x + ((long)b * HW + (long)yy * W + xx) * Cin + c0;
-      const float* wt = wl + tap * CO_CHUNK * 4;
-      for (int c8 = 0; c8 < cn; c8 += 8) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(xp + c8);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const f32x4 w0 = *reinterpret_cast<const f32x4*>(wt + (c8 + 2 * e) * 4);
-          const f32x4 w1 = *reinterpret_cast<const f32x4*>(wt + (c8 + 2 * e + 1) * 4);
-          acc += bf16lo_to_f32(v[e]) * w0;
-          acc += bf16hi_to_f32(v[e]) * w1;
-        }
-      }
-    }
-  }
+  const f32x4 acc = vae_conv_out_accumulate(x, w, wl, b, p, live, H, W, Cin);
   if (!live) return;
 #pragma unroll
   for (int co = 0; co < 4; ++co)

@@ -12,7 +12,8 @@ A submodule called on its own with another dtype or layout converts its input on
   Attn blocks       GroupNorm -> ONE q|k|v 1x1 GEMM (q rows prescaled) -> cd360_attn_single_bf16 -> proj_out 1x1 + residual x
   Upsample          cd360_conv_up2x_bf16 (nearest 2x folded into four 2x2-tap phases)
   Downsample        cd360_vae_downsample_bf16 (pad (0, 1, 0, 1) + 3x3 / stride 2; emits the next norm1's GroupNorm slab sums)
-  Decoder ends      cd360_vae_conv_in_f32 (fp32 NCHW latent in) and norm_out + SiLU -> cd360_vae_conv_out_bf16 (fp32 NCHW out)
+  Decoder ends      cd360_vae_conv_in_f32 (fp32 NCHW latent in) and norm_out + SiLU -> cd360_vae_conv_out_bf16 (fp32 NCHW out), or, for
+                    forward_u8, -> cd360_vae_conv_out_u8 (the uint8 HWC image)
   Encoder ends      cd360_vae_conv_in_f32 (fp32 NCHW image in) and norm_out + SiLU -> cd360_vae_enc_conv_out_bf16 (fp32 NCHW moments)
 
 Packed weights are cached per module, keyed on the parameters' (data_ptr, _version): load_state_dict or an in-place copy_ repacks.
@@ -434,8 +435,30 @@ class Decoder(nn.Module):
             return self._decode_pass(z, **kwargs)
         return torch.cat([self._decode_pass(z[i:i + 1], **kwargs) for i in range(z.shape[0])], 0)
 
+    @torch.no_grad()
+    def forward_u8(self, z, **kwargs):
+        """forward(z) with the image epilogue of sample.py:346 in the last kernel: [N, H, W, out_ch] uint8 (channels last, what
+        Image.fromarray takes) = (clip(forward(z) * 0.5 + 0.5, 0, 1) * 255).to(uint8) bit for bit when the parameters are fp32, without the
+        fp32 image ever reaching memory (cd360_vae_conv_out_u8).  One image per pass, as forward."""
+        self.last_z_shape = z.shape
+        if self.give_pre_end or self.tanh_out:
+            raise NotImplementedError("Decoder(give_pre_end=True | tanh_out=True) is not used by the first stage; not implemented")
+        if not z.is_cuda:
+            raise ops.Cd360Error("the first-stage HIP modules run only on the GPU; got a CPU tensor")
+        outs = []
+        for i in range(z.shape[0]):
+            act, n, hh, ww, wout, bout = self._decode_trunk(z[i:i + 1], **kwargs)
+            outs.append(ops.vae_conv_out_u8(act, wout, bout, n, hh, ww, self.conv_out.out_channels))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
     def _decode_pass(self, z, **kwargs):
         """One pass of the decoder over the whole batch z (at most max_batch(h, w) images)."""
+        act, n, hh, ww, wout, bout = self._decode_trunk(z, **kwargs)
+        out = ops.vae_conv_out(act, wout, bout, n, hh, ww, self.conv_out.out_channels)
+        return out.to(self.conv_out.weight.dtype)
+
+    def _decode_trunk(self, z, **kwargs):
+        """Everything of one pass in front of conv_out: -> (norm_out + SiLU rows [n, H W, C] bf16, n, H, W, conv_out's packed weight, bias)."""
         n, cz, h, w = z.shape
         if n > self.max_batch(h, w):
             raise ops.Cd360Error(f"{n} images of {h} x {w} exceed the 32-bit offsets of the convolution cores in one pass")
@@ -464,6 +487,4 @@ class Decoder(nn.Module):
                 hid = self.up[i_level].upsample(hid)
 
         rows, n, c, hh, ww = _rows(hid)
-        act = _gn(self.norm_out, rows, True)
-        out = ops.vae_conv_out(act, wout, bout, n, hh, ww, self.conv_out.out_channels)
-        return out.to(self.conv_out.weight.dtype)
+        return _gn(self.norm_out, rows, True), n, hh, ww, wout, bout
