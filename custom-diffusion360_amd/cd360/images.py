@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .derived import derived
 from .sampler import seed_words
 
 
@@ -26,14 +27,12 @@ def _conv1x1_pack(conv: nn.Conv2d, n_out: int, n_in: int):
     if not (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.in_channels == n_in and conv.out_channels == n_out
             and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1):
         raise ValueError(f"a 1 x 1 nn.Conv2d of {n_in} -> {n_out} channels is needed (z_channels = embed_dim = 4), got {conv}")
-    key = tuple((p.data_ptr(), p._version, p.dtype) for p in (conv.weight, conv.bias) if p is not None)
-    ent = conv.__dict__.get("_cd360_pack")
-    if ent is None or ent[0] != key:
+
+    def make():
         w = conv.weight.detach().float().reshape(n_out, n_in).contiguous()
         b = conv.bias.detach().float().contiguous() if conv.bias is not None else torch.zeros(n_out, dtype=torch.float32, device=w.device)
-        ent = (key, (w, b))
-        conv.__dict__["_cd360_pack"] = ent
-    return ent[1]
+        return w, b
+    return derived(conv, "_cd360_pack", (conv.weight, conv.bias), make)
 
 
 class FirstStage:

@@ -914,8 +914,8 @@ def gemm_ok(M: int, N: int, K: int, lda: Optional[int] = None, ldw: Optional[int
             and (M + 256) * lda * 2 < 2 ** 32 and (N + 256) * ldw * 2 < 2 ** 32)
 
 
-_F32_CACHE = {}  # id(tensor) -> (weakref, version, fp32 copy): biases of frozen Linears as the fp32 vectors the GEMM epilogue reads
-_WT_CACHE = {}   # id(weight) -> (weakref, version, weight^T contiguous): the data-gradient GEMM's operand
+_F32_CACHE = {}  # id(tensor) -> (weakref, version, data_ptr, dtype, fp32 copy): biases of frozen Linears as the fp32 vectors the GEMM epilogue reads
+_WT_CACHE = {}   # id(weight) -> (weakref, version, data_ptr, dtype, weight^T contiguous): the data-gradient GEMM's operand
 
 
 def _cached(cache: dict, t: torch.Tensor, make):
@@ -925,13 +925,13 @@ def _cached(cache: dict, t: torch.Tensor, make):
     if t.requires_grad or t._base is not None:
         return make(t)
     ent = cache.get(id(t))
-    if ent is not None and ent[0]() is t and ent[1] == t._version:
-        return ent[2]
+    if ent is not None and ent[0]() is t and ent[1] == t._version and ent[2] == t.data_ptr() and ent[3] == t.dtype:  # the rule of cd360.derived
+        return ent[4]
     if len(cache) > 4096:  # entries of tensors that died (ids are reused): drop them
         for k in [k for k, e in cache.items() if e[0]() is None]:
             del cache[k]
     val = make(t)
-    cache[id(t)] = (weakref.ref(t), t._version, val)
+    cache[id(t)] = (weakref.ref(t), t._version, t.data_ptr(), t.dtype, val)
     return val
 
 

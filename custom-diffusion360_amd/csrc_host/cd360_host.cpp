@@ -30,9 +30,11 @@ bool gemm_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw) {
          (N + 256) * ldw * 2 < (1LL << 32);
 }
 
-// frozen tensors -> derived copies (fp32 bias, transposed weight), keyed on (impl, version) like cd360/ops.py::_cached
+// frozen tensors -> derived copies (fp32 bias, transposed weight), keyed on (impl, version, data pointer, dtype) like cd360/ops.py::_cached
 struct Derived {
   uint32_t version;
+  const void* data;
+  at::ScalarType dtype;
   c10::weak_intrusive_ptr<c10::TensorImpl> owner;
   at::Tensor value;
 };
@@ -47,13 +49,14 @@ at::Tensor cached(std::unordered_map<const void*, Derived>& cache, const at::Ten
   auto it = cache.find(key);
   if (it != cache.end()) {
     auto live = it->second.owner.lock();
-    if (live && live.get() == t.unsafeGetTensorImpl() && it->second.version == t._version()) return it->second.value;
+    if (live && live.get() == t.unsafeGetTensorImpl() && it->second.version == t._version() && it->second.data == t.data_ptr() && it->second.dtype == t.scalar_type())
+      return it->second.value;
   }
   if (cache.size() > 4096) {
     for (auto i = cache.begin(); i != cache.end();) i = i->second.owner.expired() ? cache.erase(i) : std::next(i);
   }
   at::Tensor v = make(t);
-  cache.insert_or_assign(key, Derived{(uint32_t)t._version(), c10::weak_intrusive_ptr<c10::TensorImpl>(t.getIntrusivePtr()), v});
+  cache.insert_or_assign(key, Derived{(uint32_t)t._version(), t.data_ptr(), t.scalar_type(), c10::weak_intrusive_ptr<c10::TensorImpl>(t.getIntrusivePtr()), v});
   return v;
 }
 

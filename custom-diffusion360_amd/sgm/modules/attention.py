@@ -30,6 +30,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from cd360 import grad, memo, ops, routes, sample_py_patch
+from cd360.derived import derived
 from ..modules.diffusionmodules.util import HipLayerNorm, HipLinear, checkpoint, group_norm_tokens, tag_gn_stats, tokens_to_image, zero_module  # noqa: F401
 from ..modules.nerfsd_pytorch3d import NerfSDModule, VolRender
 from ..util import default, exists
@@ -224,7 +225,6 @@ class MemoryEfficientCrossAttention(nn.Module):
                 nn.init.normal_(getattr(self, f"to_{w}_attn3_down").weight, std=1 / r)
             self._lora_site = _next_lora_site()  # mask site of the adapter dropouts; BasicTransformerBlock renumbers it per block
         self.attention_op = None
-        self._merged = {}
         self._kv_cache = None
         self._kv8_cache = None  # fp8 image of the cached K / V (context_fp8)
         self.cache_context_kv = False
@@ -278,20 +278,14 @@ class MemoryEfficientCrossAttention(nn.Module):
         merge = self.lora_merge()
         if not merge and len(mods) == 1:
             return mods[0].weight
-        key = tuple((m.weight.data_ptr(), m.weight._version) for m in mods) + (mods[0].weight.dtype, mods[0].weight.device, merge)
-        if merge:
-            key = key + self.lora_key()
-        elif torch.is_grad_enabled() and any(m.weight.requires_grad for m in mods):  # trainkeys poseattn: stay on the autograd tape
+        if not merge and torch.is_grad_enabled() and any(m.weight.requires_grad for m in mods):  # trainkeys poseattn: stay on the autograd tape
             return torch.cat([m.weight for m in mods], 0)
-        cache = self._merged.get(which)
-        if cache is None or cache[0] != key:
+
+        def make():
             if merge:
-                w = torch.cat([self.lora_folded(n, m.weight) for n, m in zip(names, mods)], 0).to(mods[0].weight.dtype).contiguous()
-            else:
-                w = torch.cat([m.weight.detach() for m in mods], 0).contiguous()
-            cache = (key, w)
-            self._merged[which] = cache
-        return cache[1]
+                return torch.cat([self.lora_folded(n, m.weight) for n, m in zip(names, mods)], 0).to(mods[0].weight.dtype).contiguous()
+            return torch.cat([m.weight.detach() for m in mods], 0).contiguous()
+        return derived(self, "_merged_" + which, [m.weight for m in mods] + (self.lora_params() if merge else []), make, merge)
 
     def project_context(self, context: torch.Tensor):
         """(K, V, nk): K and V [b, Nk_pad, inner] as the two column halves of ONE [to_k; to_v] GEMM over the context (row-major V: the
@@ -420,10 +414,9 @@ class BasicTransformerBlock(nn.Module):
         self.norm2 = HipLayerNorm(dim)
         self.norm3 = HipLayerNorm(dim)
         self.checkpoint = checkpoint
-        self._pose_split = None
         self._ref_tables = None
         self._rendered_proj = None  # (rendered_feat object, its version, Wb, rendered_feat @ Wb^T) of _pose_embed_cached
-        self._pack = None  # (parameter versions, packed weights) of the fused inference path
+        self._pack = None  # cd360.derived entry of the fused inference path's frozen packs (_packed)
         self._static_rendered = self._static_proj = None  # pin_rendered()
 
     def __setattr__(self, name, value):
@@ -438,11 +431,8 @@ class BasicTransformerBlock(nn.Module):
         if torch.is_grad_enabled() and w.requires_grad:  # training: the two halves stay views of the parameter (autograd)
             c = w.shape[0]
             return w[:, :c].t(), w[:, c:].t()
-        key = (w.data_ptr(), w._version, w.dtype, w.device)
-        if self._pose_split is None or self._pose_split[0] != key:
-            c = w.shape[0]
-            self._pose_split = (key, w.detach()[:, :c].t().contiguous(), w.detach()[:, c:].t().contiguous())
-        return self._pose_split[1], self._pose_split[2]
+        c = w.shape[0]
+        return derived(self, "_pose_split", (w,), lambda: (w.detach()[:, :c].t().contiguous(), w.detach()[:, c:].t().contiguous()))
 
     def pose_embed(self, x: torch.Tensor, xref: torch.Tensor) -> torch.Tensor:
         """pose_emb_layers(cat[x, xref]) without the concat (attention.py:634): x Wa^T + xref Wb^T as two launches of the hand-written
@@ -708,16 +698,13 @@ class BasicTransformerBlock(nn.Module):
                a1.to_q.weight, a1.to_k.weight, a1.to_v.weight, a1.to_out[0].weight, a1.to_out[0].bias,
                a2.to_q.weight, a2.to_out[0].weight, a2.to_out[0].bias,
                ff.net[0].proj.weight, ff.net[0].proj.bias, ff.net[2].weight, ff.net[2].bias]
-        key = tuple((t.data_ptr(), t._version) for t in src + a1.lora_params() + a2.lora_params())  # adapters are folded into the packs
-        if self._pack is not None and self._pack[0] == key:
-            P = self._pack[1]
-            if self.image_cross:  # the one trainable source ("pose" keys): re-packed alone, the frozen entries stay (fine-tune step)
-                pw = self.pose_emb_layers.weight
-                pkey = (pw.data_ptr(), pw._version)
-                if self._pack[2] != pkey:
-                    P["pose"] = self._pack_pose()
-                    self._pack = (key, P, pkey)
-            return P
+        P = derived(self, "_pack", src + a1.lora_params() + a2.lora_params(), self._pack_frozen)  # adapters are folded into the packs
+        if self.image_cross:  # the one trainable source, a slot of its own: re-packed alone, the frozen entries stay (fine-tune step)
+            P["pose"] = derived(self, "_pack_pose_half", (self.pose_emb_layers.weight,), self._pack_pose)
+        return P
+
+    def _pack_frozen(self):
+        a1, a2, ff = self.attn1, self.attn2, self.ff
         P = {}
         # the q rows carry the softmax scale and log2(e) (ops.attention(prescaled=True)): q is rounded to bf16 once, as in the reference
         # add_lora: W' = W + U D per projection (MemoryEfficientCrossAttention.lora_folded), in fp32 before the packs' one rounding
@@ -730,11 +717,6 @@ class BasicTransformerBlock(nn.Module):
         perm = ops.geglu_row_order(w.shape[0] // 2, w.device)
         P["ff1"] = (w[perm].contiguous(), ws[perm].contiguous(), cb[perm].contiguous())
         P["ff2"] = (ff.net[2].weight.detach().to(torch.bfloat16).contiguous(), ff.net[2].bias.detach().float().contiguous())
-        pkey = None
-        if self.image_cross:
-            pw = self.pose_emb_layers.weight
-            P["pose"], pkey = self._pack_pose(), (pw.data_ptr(), pw._version)
-        self._pack = (key, P, pkey)
         return P
 
     def _pack_pose(self):
@@ -921,7 +903,6 @@ class SpatialTransformer(nn.Module):
             for d in range(depth)])
         self.proj_out = zero_module(HipLinear(inner_dim, in_channels))
         self.use_linear = use_linear
-        self._ppack = None
 
     def __setattr__(self, name, value):
         if name == "forward" and _sample_py_patch_kind(value) == "st":
@@ -971,10 +952,7 @@ class SpatialTransformer(nn.Module):
 
     def _proj_pack(self):
         ps = (self.proj_in.weight, self.proj_in.bias, self.proj_out.weight, self.proj_out.bias)
-        key = tuple((t.data_ptr(), t._version) for t in ps)
-        if self._ppack is None or self._ppack[0] != key:
-            self._ppack = (key, tuple(t.detach().to(torch.bfloat16 if t.dim() == 2 else torch.float32).contiguous() for t in ps))
-        return self._ppack[1]
+        return derived(self, "_ppack", ps, lambda: tuple(t.detach().to(torch.bfloat16 if t.dim() == 2 else torch.float32).contiguous() for t in ps))
 
     def _enter(self, img):
         """GroupNorm -> proj_in on the fused path: tokens [b, hw, inner] and their LayerNorm row statistics (from the GEMM's epilogue)."""

@@ -16,8 +16,7 @@ A submodule called on its own with another dtype or layout converts its input on
                     forward_u8, -> cd360_vae_conv_out_u8 (the uint8 HWC image)
   Encoder ends      cd360_vae_conv_in_f32 (fp32 NCHW image in) and norm_out + SiLU -> cd360_vae_enc_conv_out_bf16 (fp32 NCHW moments)
 
-Packed weights are cached per module, keyed on the parameters' (data_ptr, _version): load_state_dict or an in-place copy_ repacks.
-An edit through `p.data` is NOT seen: `.data` is a tensor with a version counter of its own (as for UNetModel._emb_cat).
+Packed weights are cached per module by cd360.derived.derived: its docstring states when they are rebuilt, and the one edit it cannot see.
 Forward only: a call autograd would have to record raises (decode_first_stage and encode_first_stage run under no_grad)."""
 from __future__ import annotations
 
@@ -25,6 +24,8 @@ import torch
 import torch.nn as nn
 
 from cd360 import ops
+from cd360.derived import derived
+from .util import _tagged_gn_stats, tag_gn_stats
 
 _INT32_BYTES = 2 ** 31  # the convolution cores address one operand with 32-bit byte offsets (cd360_conv_igemm_bf16)
 
@@ -59,34 +60,19 @@ def _nchw(rows: torch.Tensor, n: int, h: int, w: int) -> torch.Tensor:
     return rows.view(n, h, w, rows.shape[-1]).permute(0, 3, 1, 2)
 
 
-def _with_stats(t: torch.Tensor, stats) -> torch.Tensor:
-    """Attach the GroupNorm slab sums a kernel produced while writing t (consumed by the next block's first GroupNorm)."""
-    if stats is not None:
-        t._cd360_gn_stats = (t._version, stats)
-    return t
-
-
-def _stats_of(t: torch.Tensor):
-    ent = getattr(t, "_cd360_gn_stats", None)
-    return ent[1] if ent is not None and ent[0] == t._version else None
-
-
-def _packed(mod: nn.Module, params, make):
-    """make() cached on mod, keyed on every parameter's (data_ptr, _version, dtype)."""
-    key = tuple((p.data_ptr(), p._version, p.dtype) for p in params if p is not None)
-    ent = mod.__dict__.get("_cd360_pack")
-    if ent is None or ent[0] != key:
-        ent = (key, make())
-        mod.__dict__["_cd360_pack"] = ent
-    return ent[1]
-
-
 def _gn(norm: nn.GroupNorm, rows: torch.Tensor, silu: bool, tile_stats=None, out=None) -> torch.Tensor:
     return ops.gn_silu(rows, ops.bias_f32(norm.weight), ops.bias_f32(norm.bias), norm.num_groups, norm.eps, silu, out=out, tile_stats=tile_stats)
 
 
 def _conv_pack(conv: nn.Conv2d):
     return ops.pack_conv_weight(conv.weight), ops.bias_f32(conv.bias).clone() if conv.bias is not None else None
+
+
+def _ends_pack(net: nn.Module, pack_out):
+    """(conv_in weight, bias, conv_out weight, bias) of an Encoder / Decoder as its two end kernels read them."""
+    ci, co = net.conv_in, net.conv_out
+    return derived(net, "_cd360_pack", (ci.weight, ci.bias, co.weight, co.bias), lambda: (
+        ops.pack_vae_conv_in_weight(ci.weight), ops.bias_f32(ci.bias).clone(), pack_out(co.weight), ops.bias_f32(co.bias).clone()))
 
 
 # ----------------------------------------------------------------------------------------------- blocks
@@ -97,13 +83,16 @@ class Upsample(nn.Module):
         if self.with_conv:
             self.conv = torch.nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=1, padding=1)
 
+    def _pack(self):
+        return derived(self, "_cd360_pack", (self.conv.weight, self.conv.bias),
+                       lambda: (ops.pack_upsample_conv_weight(self.conv.weight), ops.bias_f32(self.conv.bias).clone()))
+
     def forward(self, x):
         if not self.with_conv:
             raise NotImplementedError("Upsample(with_conv=False) is not used by the first stage (resamp_with_conv=True)")
         _check_no_grad(self)
         rows, n, c, h, w = _rows(x)
-        wph, b = _packed(self, (self.conv.weight, self.conv.bias),
-                         lambda: (ops.pack_upsample_conv_weight(self.conv.weight), ops.bias_f32(self.conv.bias).clone()))
+        wph, b = self._pack()
         return _nchw(ops.conv_up2x(rows, wph, b, n, h, w), n, 2 * h, 2 * w)
 
 
@@ -115,14 +104,17 @@ class Downsample(nn.Module):
             # no asymmetric padding in torch conv, must do it ourselves
             self.conv = torch.nn.Conv2d(in_channels, in_channels, kernel_size=3, stride=2, padding=0)
 
+    def _pack(self):
+        return derived(self, "_cd360_pack", (self.conv.weight, self.conv.bias), lambda: _conv_pack(self.conv))
+
     def forward(self, x):
         if not self.with_conv:
             raise NotImplementedError("Downsample(with_conv=False) is not used by the first stage (resamp_with_conv=True)")
         _check_no_grad(self)
         rows, n, c, h, w = _rows(x)
-        wp, b = _packed(self, (self.conv.weight, self.conv.bias), lambda: _conv_pack(self.conv))
+        wp, b = self._pack()
         out, st = ops.vae_downsample(rows, wp, b, n, h, w)
-        return _with_stats(_nchw(out, n, h // 2, w // 2), st)
+        return tag_gn_stats(_nchw(out, n, h // 2, w // 2), st)
 
 
 class ResnetBlock(nn.Module):
@@ -151,6 +143,11 @@ class ResnetBlock(nn.Module):
             return None
         return self.conv_shortcut if self.use_conv_shortcut else self.nin_shortcut
 
+    def _packs(self):
+        sc = self._shortcut()
+        convs = (self.conv1, self.conv2) + ((sc,) if sc is not None else ())
+        return derived(self, "_cd360_pack", [p for m in convs for p in (m.weight, m.bias)], lambda: [_conv_pack(m) for m in convs])
+
     def forward(self, x, temb=None, **kwargs):
         if temb is not None:
             raise NotImplementedError("ResnetBlock with a time embedding (Model); the first stage passes temb=None")
@@ -158,10 +155,8 @@ class ResnetBlock(nn.Module):
             raise NotImplementedError("ResnetBlock dropout > 0 in train mode (the first stage's config has dropout 0)")
         _check_no_grad(self)
         rows, n, c, h, w = _rows(x)
-        sc = self._shortcut()
-        convs = (self.conv1, self.conv2) + ((sc,) if sc is not None else ())
-        packs = _packed(self, [p for m in convs for p in (m.weight, m.bias)], lambda: [_conv_pack(m) for m in convs])
-        hid = _gn(self.norm1, rows, True, tile_stats=_stats_of(x))
+        sc, packs = self._shortcut(), self._packs()
+        hid = _gn(self.norm1, rows, True, tile_stats=_tagged_gn_stats(x))
         if (h * w) % 128 == 0:
             hid, st = ops.conv_igemm(hid, packs[0][0], packs[0][1], n, h, w, 9, want_stats=True)
         else:
@@ -191,7 +186,7 @@ class _SingleHeadAttn(nn.Module):
             wqkv, bqkv = ops.pack_attn_qkv(self.q.weight, self.q.bias, self.k.weight, self.k.bias, self.v.weight, self.v.bias)
             return wqkv, bqkv, self.proj_out.weight.detach().reshape(self.in_channels, -1).to(torch.bfloat16).contiguous(), \
                 ops.bias_f32(self.proj_out.bias).clone()
-        return _packed(self, [p for m in (self.q, self.k, self.v, self.proj_out) for p in (m.weight, m.bias)], make)
+        return derived(self, "_cd360_pack", [p for m in (self.q, self.k, self.v, self.proj_out) for p in (m.weight, m.bias)], make)
 
     def forward(self, x, **kwargs):
         _check_no_grad(self)
@@ -305,15 +300,13 @@ class Encoder(nn.Module):
             raise ops.Cd360Error(f"an image of {h} x {w} exceeds the 32-bit offsets of the convolution cores")
         temb = None
 
-        win, bin_, wout, bout = _packed(self, (self.conv_in.weight, self.conv_in.bias, self.conv_out.weight, self.conv_out.bias), lambda: (
-            ops.pack_vae_conv_in_weight(self.conv_in.weight), ops.bias_f32(self.conv_in.bias).clone(),
-            ops.pack_vae_enc_conv_out_weight(self.conv_out.weight), ops.bias_f32(self.conv_out.bias).clone()))
+        win, bin_, wout, bout = _ends_pack(self, ops.pack_vae_enc_conv_out_weight)
         x32 = x.float().contiguous()
         if (h * w) % 64 == 0:
             rows, st = ops.vae_conv_in(x32, win, bin_, want_stats=True)
         else:
             rows, st = ops.vae_conv_in(x32, win, bin_), None
-        hid = _with_stats(_nchw(rows, n, h, w), st)
+        hid = tag_gn_stats(_nchw(rows, n, h, w), st)
 
         # the reference keeps every level's output in a list `hs`; only its last entry is ever read
         for i_level in range(self.num_resolutions):
@@ -464,15 +457,13 @@ class Decoder(nn.Module):
             raise ops.Cd360Error(f"{n} images of {h} x {w} exceed the 32-bit offsets of the convolution cores in one pass")
         temb = None
 
-        win, bin_, wout, bout = _packed(self, (self.conv_in.weight, self.conv_in.bias, self.conv_out.weight, self.conv_out.bias), lambda: (
-            ops.pack_vae_conv_in_weight(self.conv_in.weight), ops.bias_f32(self.conv_in.bias).clone(),
-            ops.pack_vae_conv_out_weight(self.conv_out.weight), ops.bias_f32(self.conv_out.bias).clone()))
+        win, bin_, wout, bout = _ends_pack(self, ops.pack_vae_conv_out_weight)
         z32 = z.float().contiguous()
         if (h * w) % 64 == 0:
             rows, st = ops.vae_conv_in(z32, win, bin_, want_stats=True)
         else:
             rows, st = ops.vae_conv_in(z32, win, bin_), None
-        hid = _with_stats(_nchw(rows, n, h, w), st)
+        hid = tag_gn_stats(_nchw(rows, n, h, w), st)
 
         hid = self.mid.block_1(hid, temb, **kwargs)
         hid = self.mid.attn_1(hid, **kwargs)

@@ -21,6 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from cd360 import ops, routes
+from cd360.derived import derived
 from ...modules.attention import SpatialTransformer
 from ...modules.diffusionmodules.util import (
     conv_image,
@@ -99,10 +100,7 @@ class Upsample(nn.Module):
     def _phase_weights(self):
         """The conv's weight as four 2 x 2-tap phase kernels (ops.pack_upsample_conv_weight), rebuilt when the parameters change."""
         w, b = self.conv.weight, self.conv.bias
-        key = (w.data_ptr(), w._version, None if b is None else b._version)
-        if getattr(self, "_up_pack", None) is None or self._up_pack[0] != key:
-            self._up_pack = (key, ops.pack_upsample_conv_weight(w), None if b is None else b.detach().float().contiguous())
-        return self._up_pack[1], self._up_pack[2]
+        return derived(self, "_up_pack", (w, b), lambda: (ops.pack_upsample_conv_weight(w), None if b is None else b.detach().float().contiguous()))
 
     def forward(self, x):
         assert x.shape[1] == self.channels
@@ -283,7 +281,6 @@ class UNetModel(nn.Module):
                 self.output_blocks.append(TimestepEmbedSequential(*layers))
 
         self.out = nn.Sequential(normalization(ch), nn.SiLU(), zero_module(conv_nd(dims, model_channels, out_channels, 3, padding=1)))
-        self._emb_cat = None  # (key, concatenated emb_layers weights, biases) of _tag_emb_outs
         self._last_pose_out = None  # index of the last output block holding a pose block (set on first forward)
 
     @property
@@ -297,27 +294,18 @@ class UNetModel(nn.Module):
         a ResBlock that does not find its slice computes its own projection as before."""
         if not (emb.is_cuda and emb.dtype == torch.bfloat16) or torch.is_grad_enabled() or routes.no_emb_merge:
             return emb
-        blocks = [m for m in self.modules() if isinstance(m, ResBlock)]
-        key = tuple((b.emb_layers[1].weight.data_ptr(), b.emb_layers[1].weight._version, b.emb_layers[1].bias._version) for b in blocks)
-        if self._emb_cat is None or self._emb_cat[0] != key:
-            w = torch.cat([b.emb_layers[1].weight.detach() for b in blocks], 0).contiguous()
-            bias = torch.cat([b.emb_layers[1].bias.detach() for b in blocks], 0).contiguous()
-            self._emb_cat = (key, w, bias)
-        return self._emb_outs_from_act(torch.nn.functional.silu(emb), emb, blocks)
+        return self._emb_outs_from_act(torch.nn.functional.silu(emb), emb)
 
-    def _emb_outs_from_act(self, act: torch.Tensor, emb: torch.Tensor, blocks=None) -> torch.Tensor:
+    def _emb_outs_from_act(self, act: torch.Tensor, emb: torch.Tensor) -> torch.Tensor:
         """The merged emb_layers GEMM on act = silu(emb); the per-block column slices ride on `emb` (see _tag_emb_outs)."""
-        if blocks is None:
-            blocks = [m for m in self.modules() if isinstance(m, ResBlock)]
-            key = tuple((b.emb_layers[1].weight.data_ptr(), b.emb_layers[1].weight._version, b.emb_layers[1].bias._version) for b in blocks)
-            if self._emb_cat is None or self._emb_cat[0] != key:
-                w = torch.cat([b.emb_layers[1].weight.detach() for b in blocks], 0).contiguous()
-                bias = torch.cat([b.emb_layers[1].bias.detach() for b in blocks], 0).contiguous()
-                self._emb_cat = (key, w, bias)
-        if ops.linear_ok(act, self._emb_cat[1]) and not routes.library_linear:
-            allp = ops.linear(act, self._emb_cat[1], self._emb_cat[2])  # [b, sum(out_channels)] on the hand-written GEMM (M = batch rows)
+        blocks = [m for m in self.modules() if isinstance(m, ResBlock)]
+        lins = [b.emb_layers[1] for b in blocks]
+        w, bias = derived(self, "_emb_cat", [p for m in lins for p in (m.weight, m.bias)], lambda: (
+            torch.cat([m.weight.detach() for m in lins], 0).contiguous(), torch.cat([m.bias.detach() for m in lins], 0).contiguous()))
+        if ops.linear_ok(act, w) and not routes.library_linear:
+            allp = ops.linear(act, w, bias)  # [b, sum(out_channels)] on the hand-written GEMM (M = batch rows)
         else:
-            allp = torch.nn.functional.linear(act, self._emb_cat[1], self._emb_cat[2])
+            allp = torch.nn.functional.linear(act, w, bias)
         outs, off = {}, 0
         for blk in blocks:
             c = blk.out_channels
@@ -423,6 +411,11 @@ class UNetModel(nn.Module):
         t = group_norm_tokens(self.out[0], h, silu=True)
         return self._out_conv_tokens(t, h.shape[0], H, W)
 
+    def _out_conv4_pack(self):
+        w, b = self.out[2].weight, self.out[2].bias
+        return derived(self, "_out4_pack", (w, b), lambda: (
+            ops.pack_out_conv4_weight(w), b.detach().float().contiguous() if b is not None else torch.zeros(4, device=w.device)))
+
     def _out_conv_tokens(self, t, N: int, H: int, W: int):
         """self.out[2] (Conv2d(model_channels -> out_channels, 3 x 3, padding 1), openaimodel.py:967-973) on activated tokens [N, H W, C] ->
         [N, H W, out_channels]: four output channels at an image width the small kernel serves go to cd360_out_conv4_bf16 (one pass over the
@@ -431,10 +424,6 @@ class UNetModel(nn.Module):
         if (conv.out_channels == 4 and conv.kernel_size == (3, 3) and conv.padding == (1, 1) and conv.stride == (1, 1) and t.is_cuda
                 and t.dtype == torch.bfloat16 and conv.weight.dtype == torch.bfloat16 and ops.out_conv4_ok(H, W, conv.in_channels)
                 and not torch.is_grad_enabled() and not routes.edge_convs_miopen and not routes.no_out_conv4 and conv.groups == 1 and conv.dilation == (1, 1)):
-            w, b = conv.weight, conv.bias
-            key = (w.data_ptr(), w._version, None if b is None else b._version)
-            if getattr(self, "_out4_pack", None) is None or self._out4_pack[0] != key:
-                bias = b.detach().float().contiguous() if b is not None else torch.zeros(4, device=w.device)
-                self._out4_pack = (key, ops.pack_out_conv4_weight(w), bias)
-            return ops.out_conv4(t.contiguous(), self._out4_pack[1], self._out4_pack[2], N, H, W)
+            w4, bias = self._out_conv4_pack()
+            return ops.out_conv4(t.contiguous(), w4, bias, N, H, W)
         return conv_tokens(conv, t, N, H, W)

@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from cd360 import ops, routes
+from cd360.derived import derived
 
 
 def checkpoint(func, inputs, params, flag):
@@ -53,12 +54,8 @@ def mean_flat(tensor):
 
 def _fp32_affine(norm: nn.GroupNorm):
     """fp32 copies of gamma/beta for the kernel, refreshed when the parameters change."""
-    key = (norm.weight.data_ptr(), norm.weight._version, norm.bias._version, norm.weight.device)
-    cache = getattr(norm, "_cd360_affine", None)
-    if cache is None or cache[0] != key:
-        cache = (key, norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous())
-        norm._cd360_affine = cache
-    return cache[1], cache[2]
+    return derived(norm, "_cd360_affine", (norm.weight, norm.bias),
+                   lambda: (norm.weight.detach().float().contiguous(), norm.bias.detach().float().contiguous()))
 
 
 def tag_gn_stats(img: torch.Tensor, stats) -> torch.Tensor:
@@ -121,9 +118,8 @@ def packed_conv(conv: nn.Conv2d):
     ok1 = k == (1, 1) and conv.padding == (0, 0) and conv.stride == (1, 1)
     if not (w.is_cuda and (ok3 or ok1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros"):
         return None
-    key = (w.data_ptr(), w._version, w.dtype, w.device, None if conv.bias is None else conv.bias._version)
-    cache = getattr(conv, "_cd360_packed", None)
-    if cache is None or cache[0] != key:
+
+    def make():
         cout, cin = w.shape[:2]
         cin_p, cout_p = -(-cin // 64) * 64, -(-cout // 16) * 16
         wd = w.detach()
@@ -132,9 +128,8 @@ def packed_conv(conv: nn.Conv2d):
         bias = None
         if conv.bias is not None:
             bias = torch.nn.functional.pad(conv.bias.detach().float(), (0, cout_p - cout)).contiguous()
-        cache = (key, ops.pack_conv_weight(wd), bias)
-        conv._cd360_packed = cache
-    return cache[1], cache[2]
+        return ops.pack_conv_weight(wd), bias
+    return derived(conv, "_cd360_packed", (w, conv.bias), make)
 
 
 def packed_conv_dgrad(conv: nn.Conv2d):
@@ -143,16 +138,14 @@ def packed_conv_dgrad(conv: nn.Conv2d):
     As an igemm weight its input channels (= Cout, padded like packed_conv's outputs) are zero-padded to a multiple of 64 and its
     output channels (= Cin padded to 64 by packed_conv) kept.  Cached on the module like packed_conv."""
     w = conv.weight
-    key = (w.data_ptr(), w._version, w.dtype, w.device)
-    cache = getattr(conv, "_cd360_packed_dgrad", None)
-    if cache is None or cache[0] != key:
+
+    def make():
         cout, cin = w.shape[:2]
         cin_p, cout_p = -(-cin // 64) * 64, -(-(-(-cout // 16) * 16) // 64) * 64
         wt = w.detach().flip(2, 3).transpose(0, 1)  # [cin, cout, k, k]
         wt = torch.nn.functional.pad(wt, (0, 0, 0, 0, 0, cout_p - cout, 0, cin_p - cin))
-        cache = (key, ops.pack_conv_weight(wt.contiguous()))
-        conv._cd360_packed_dgrad = cache
-    return cache[1]
+        return ops.pack_conv_weight(wt.contiguous())
+    return derived(conv, "_cd360_packed_dgrad", (w,), make)
 
 
 def _frozen(conv: nn.Conv2d) -> bool:

@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from cd360 import nerf as _nerf
 from cd360 import ops
+from cd360.derived import derived
 from ..modules.diffusionmodules.util import zero_module
 from ..modules.utils_cameraray import packed_pose
 
@@ -37,12 +38,11 @@ class FeatureNeRFEncoding(nn.Module):
         self.plane_coefs = nn.Sequential(nn.Linear(e, out_channels), nn.SiLU(), nn.Linear(out_channels, out_channels))
         self.nviews = nn.Linear(e, 1)
         self.decoder = zero_module(nn.Linear(out_channels, 1 + (3 if rgb_predict else 0), bias=False))
-        self._fused = None
 
     def fused_weights(self) -> _nerf.FusedNerfWeights:
         ps = [self.plane_coefs[0].weight, self.plane_coefs[0].bias, self.plane_coefs[2].weight, self.plane_coefs[2].bias,
               self.nviews.weight, self.nviews.bias, self.decoder.weight]
-        key = tuple((p.data_ptr(), p._version, p.device, p.dtype) for p in ps)
+        src = tuple(ps)
         if self.average:
             # nerfsd_pytorch3d.py:156-158: the views are averaged instead of softmax-weighted.  A zero `nviews` makes every view logit 0,
             # the in-kernel view softmax uniform = the mean (and, as in the reference, nviews then receives no gradient)
@@ -52,12 +52,13 @@ class FeatureNeRFEncoding(nn.Module):
             if wd.shape[0] == 1:
                 wd = torch.cat([torch.zeros(3, wd.shape[1], device=wd.device, dtype=wd.dtype), wd], 0)
             return _nerf.FusedNerfWeights(ps[0], ps[1], ps[2], ps[3], ps[4], ps[5], wd, live=True)
-        if self._fused is None or self._fused[0] != key:
+
+        def make():
             wd = self.decoder.weight
             if wd.shape[0] == 1:  # rgb_predict False: only sigma; pad rgb rows with zeros (row 3 = sigma)
                 wd = torch.cat([torch.zeros(3, wd.shape[1], device=wd.device, dtype=wd.dtype), wd], 0)
-            self._fused = (key, _nerf.FusedNerfWeights(ps[0], ps[1], ps[2], ps[3], ps[4], ps[5], wd))
-        return self._fused[1]
+            return _nerf.FusedNerfWeights(ps[0], ps[1], ps[2], ps[3], ps[4], ps[5], wd)
+        return derived(self, "_fused", src, make)
 
     def forward(self, pose, xref, ray_points, rays, mask_ref):
         raise NotImplementedError(
