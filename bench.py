@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Headline benchmark: UNet denoise steps/s at SDXL 1024^2 with 50 reference views (BASELINE.json configs[1]).
 
-    python bench.py --gpus 1 --steps 50 --warmup 3
+    python bench.py --gpus 1 --steps 50 --warmup 3           # the headline figure and nothing else
+    python bench.py --gpus 1 --steps 50 --warmup 3 --full    # plus everything else the benchmark measures (below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload ("sample.py 50-step sampling, SDXL 1024^2, 50-view synthetic cameras"): random-init SDXL UNet from the reference's
@@ -11,6 +12,11 @@ CFG batch plus the CFG combine and Euler update.  The timed region walks the sam
 trajectory runs the 12 FeatureNeRF renders, the other 49 use the cached render (sample.py:122-133), so with --steps 50 the
 timed region is exactly one image.  Multi-GPU = independent target poses (weak scaling), one RCCL all-gather of the final
 latents at the end of the job (outside the per-step path).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: `roofline` is null, `rooflines` and
+`config.kernel_ms_per_step` are empty.  --full appends, after the timed region, every measurement that takes runs of its own:
+the per-kernel HIP-event replay behind `roofline` / `rooflines` / `config.kernel_ms_per_step`, `config.reference_tables_ms`, the
+`fp8_tolerance` comparison of --fp8-attn, `train_step` and `cpu_baseline` (each still switched off by its --no-... option).
 """
 from __future__ import annotations
 
@@ -155,8 +161,11 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path returned from its last step -- "
                     "the final latents of every pose of the job, [poses, 4, latent, latent] -- as DIR/latents.npy (float32, at most 64 MB in "
                     "all).  The inputs depend on the arguments alone, so two builds run with the same arguments compare output for output")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip per-kernel HIP-event timing")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run everything else the benchmark measures: per-kernel HIP-event "
+                    "timing and the rooflines, the reference-table cost, the fine-tuning step, the CPU baseline and, with --fp8-attn, the comparison "
+                    "with the bf16 run.  Off by default: a plain run stops at the headline figure")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip per-kernel HIP-event timing")
     ap.add_argument("--no-graph", action="store_true", help="launch every step eagerly instead of replaying the steady-state step from a hipGraph")
     ap.add_argument("--route", choices=["fused", "hooked", "module", "sample_py"], default="fused",
                     help="hooked: a no-op forward hook on every transformer BLOCK (what the references harvest registers, diffusion.py:151-163): "
@@ -165,16 +174,20 @@ def main():
                     "submodule through the module protocol, same kernels, un-fused.  sample_py: `forward` rebound on every SpatialTransformer / block "
                     "instance the way the UNCHANGED sample.py does it (sample.py:247-278; stand-in functions of tests/golden/sample_py_stub.py), "
                     "no call into cd360.sampling: the rebinding is recognised and served by the fused route")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the fine-tuning step measurement appended after the timed region (BASELINE configs[3])")
+    ap.add_argument("--no-train-step", action="store_true", help="with --full: skip the fine-tuning step measurement appended after the timed region (BASELINE configs[3])")
     ap.add_argument("--no-weight-prefetch", action="store_true", help="capture the steps without the weight prefetcher (cd360/prefetch.py): the A/B partner")
     ap.add_argument("--prefetch-wgs", type=int, default=256)
     ap.add_argument("--prefetch-lag", type=int, default=2)
     ap.add_argument("--prefetch-min-mb", type=float, default=0.25)
     ap.add_argument("--fp8-attn", action="store_true", help="BASELINE configs[4]: the text / pose-token cross-attention of every block with q K^T and P V on "
-                    "fp8 MFMA (cd360_qproj_attn_fp8_bf16) for the whole run; adds an `fp8_tolerance` object (rendered features and eps against the bf16 run)")
+                    "fp8 MFMA (cd360_qproj_attn_fp8_bf16) for the whole run; with --full adds an `fp8_tolerance` object (rendered features and eps against the bf16 run)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1: it is the number of timed steps")
+    # what only --full runs (all of it after the timed region; none of it feeds value / ms_per_step or the dumped latents)
+    do_profile = args.full and not args.no_profile
+    do_train_step = args.full and not args.no_train_step
+    do_cpu_baseline = args.full and not args.no_cpu_baseline
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: become the launcher.  The same command line is re-run as N ranks (one per GPU) under
@@ -244,7 +257,8 @@ def main():
     xw = x.clone()
     for i in range(args.warmup):
         xw = smp.step(xw, i)
-    # individually timed render / steady steps (reported in config, not the headline)
+    # individually timed render / steady steps (reported in config, not the headline).  Two steps, a tenth of a second: a plain run keeps them,
+    # so the timed region below follows the same launches as ever, whatever --warmup says
     sync(); t0 = time.perf_counter(); xw = smp.step(x.clone(), 0); sync(); render_ms = (time.perf_counter() - t0) * 1e3
     t0 = time.perf_counter(); xw = smp.step(xw, 1); sync(); steady_ms = (time.perf_counter() - t0) * 1e3
 
@@ -262,7 +276,7 @@ def main():
     # Per-kernel HIP-event timing: the SAME K steps replayed eagerly right after the timed region (events cannot bracket kernels
     # inside a hipGraph replay, and ~800 event records per step would otherwise sit inside the headline number).
     prof = {}
-    if not args.no_profile and rank == 0:
+    if do_profile and rank == 0:
         smp.use_graph = False
         ops.profile_start()
         xp = x.clone()
@@ -275,7 +289,7 @@ def main():
     # images per pose block) are built once per job in Sampler.prepare(), outside the timed region.  Two eager render steps after the
     # timed region, the second with every block's tables dropped first, give their cost on this box.
     tables_ms = None
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and do_profile:
         from cd360 import sampling as _smp
         smp.use_graph = False
         sync_ = torch.cuda.synchronize
@@ -311,12 +325,14 @@ def main():
         # ---- rooflines.  `achieved` = ALGORITHMIC flops (MFMA-bound kernels) or bytes (HBM-bound) of the launches / their HIP-event time on
         # the launch stream (ops._timed: SURVEY.md section 8d formulas, stated per kernel in DESIGN.md section 7b) ----
         MFMA_KERNELS = {"gemm8p", "qproj_attn", "qproj_attn_text", "attn_self", "conv_igemm", "nerf_mlp_aggregate"}
-        try:
-            from cd360 import _lib
-            with open(_lib.LIB_PATH, "rb") as f:
-                lib_bytes = f.read()
-        except Exception:  # noqa: BLE001
-            lib_bytes = b""
+        lib_bytes = b""
+        if prof:  # (only the traffic figures of the rooflines look into the library)
+            try:
+                from cd360 import _lib
+                with open(_lib.LIB_PATH, "rb") as f:
+                    lib_bytes = f.read()
+            except Exception:  # noqa: BLE001
+                pass
 
         def roofline_of(name):
             e = prof[name]
@@ -424,7 +440,7 @@ def main():
             "roofline": roof,
             "rooflines": roofs,
         }
-        if args.fp8_attn:
+        if args.fp8_attn and args.full:
             # BASELINE configs[4] tolerance report at workload level: the same render step (all 12 FeatureNeRF renders, pose-token attention
             # over 98 304 / 24 576 tokens per branch) and one cached step, launched eagerly, with the attention contractions in bf16 and in fp8
             from cd360 import sampling
@@ -448,7 +464,7 @@ def main():
                                             "two attention contractions differs; against the fp32 oracle on a ray subset: "
                                             "tests/test_modules_gpu.py::test_cfgB_pose_block_render_fp8_attention_tolerance_report"}
             smp.use_graph = not args.no_graph
-        if world == 1 and not args.no_train_step:
+        if world == 1 and do_train_step:
             # BASELINE configs[3] under the driver's eyes: one fine-tuning optimisation step at SDXL size (512^2 images, batch 4, 4 reference
             # views, trainkeys = pose: forward of both streams, four-term loss, backward, AdamW on fp32 masters) -- one warm + three timed
             # steps on the hand-written GEMM family (cd360_ms), then the same with every Linear on torch / hipBLASLt (library_ms)
@@ -473,7 +489,7 @@ def main():
                                              "cd360_gemm_tn_bf16 (forward, dgrad, wgrad); library_ms = eager with the Linears on torch (hipBLASLt)"}
             except Exception as e:  # noqa: BLE001
                 out["train_step"] = {"ms": None, "error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and do_cpu_baseline:
             try:
                 # 32 threads: PyTorch's CPU kernels stop scaling (and regress badly) beyond one socket's worth of cores
                 out["cpu_baseline"] = cpu_baseline(net, args.latent, min(os.cpu_count() or 1, 32))

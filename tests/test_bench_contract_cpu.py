@@ -1,6 +1,7 @@
-"""The bench line's contract, checked on the newest committed line of `python bench.py --steps 20 --warmup 5` (profiles/*_bench_20steps_warmup5.json:
-what the driver parses) and on bench.py's argument defaults -- no GPU needed.  Guards the key set, the metric / unit of BASELINE.json, the
-roofline arithmetic (frac = achieved / peak; peak from MI355X_MICROARCH.md: 2.5 PFLOP/s dense bf16, 8 TB/s HBM) and the cpu_baseline object."""
+"""The bench line's contract, checked on the newest committed line of `python bench.py --steps 20 --warmup 5 --full` (profiles/*_bench_20steps_warmup5.json:
+the lines committed so far were written when every run measured what --full now adds) and on bench.py's argument defaults -- no GPU needed.
+Guards the key set, the metric / unit of BASELINE.json, the roofline arithmetic (frac = achieved / peak; peak from MI355X_MICROARCH.md:
+2.5 PFLOP/s dense bf16, 8 TB/s HBM), the cpu_baseline object, and that a run without --full stops at the headline figure."""
 import glob
 import json
 import os
@@ -63,6 +64,25 @@ def test_bench_defaults_finish_quickly():
     steps = re.search(r'add_argument\("--steps", type=int, default=(\d+)', src)
     warm = re.search(r'add_argument\("--warmup", type=int, default=(\d+)', src)
     assert gpus and int(gpus.group(1)) == 1 and steps and int(steps.group(1)) <= 100 and warm and int(warm.group(1)) <= 10
+
+
+def test_bench_full_is_an_option_that_is_off_and_gates_every_extra_measurement():
+    """--full exists, is a plain switch (off unless given), and every measurement beyond the headline figure -- the per-kernel replay, the
+    reference-table steps, the fp8 comparison, the fine-tuning step, the CPU baseline -- runs only under it; the --no-... options can only
+    take away from --full, never switch something on by their absence."""
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert re.search(r'add_argument\("--full", action="store_true"', src)
+    for name in ("profile", "train_step", "cpu_baseline"):
+        assert re.search(rf"do_{name} = args\.full and not args\.no_{name}\b", src), name
+    body = src[src.index("def main():"):]
+    uses = re.findall(r"^\s*(?:el)?if [^\n]*\bargs\.no_(?:profile|train_step|cpu_baseline)\b[^\n]*:", body, flags=re.M)
+    assert not uses, uses  # no branch asks a --no-... option directly: they act through the do_* switches above
+    assert "if do_profile and rank == 0:" in body and "if rank == 0 and do_profile:" in body
+    assert "if args.fp8_attn and args.full:" in body and "if world == 1 and do_train_step:" in body and "if world == 1 and do_cpu_baseline:" in body
+    for heavy in ("ops.profile_start()", "import bench_train", "cpu_baseline(net,", "path_outputs(False)", "blk._ref_tables = None"):
+        at = body.index(heavy)
+        gates = [m.start() for m in re.finditer(r"if [^\n]*(?:do_profile|do_train_step|do_cpu_baseline|args\.full)[^\n]*:\n", body[:at])]
+        assert gates and body.index("finals = sample_assigned(", 0) < gates[-1] < at, heavy  # gated, and after the timed region
 
 
 def test_bench_gpus_n_launches_its_own_ranks():

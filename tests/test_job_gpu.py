@@ -184,3 +184,35 @@ def test_bench_dump_outputs_repeats_run_for_run(tmp_path):
     assert a.dtype == np.float32 and a.shape == (2, 4, 32, 32) and np.isfinite(a).all() and a.std() > 0
     assert not np.array_equal(a[0], a[1])  # two target poses, two start latents
     assert np.allclose(a, b, rtol=0, atol=1e-5 * float(np.abs(a).max())), float(np.abs(a - b).max())
+
+
+def test_bench_plain_run_stops_at_the_headline_and_full_adds_the_rest(tmp_path):
+    """`bench.py` without --full sets up, warms up, times the steps, dumps and prints: no per-kernel figures, no rooflines, no CPU baseline,
+    no fine-tuning step, no fp8 comparison.  The same command with --full prints all of these next to the same headline keys, and what it
+    measures after the timed steps does not reach the outputs: both runs dump the same latents.  (--no-train-step: the fine-tuning step at
+    SDXL size takes longer than a test may; `--full` with it runs in the benchmark's own --full run.)"""
+    import numpy as np
+    lines = {}
+    for run, extra in (("plain", []), ("full", ["--full", "--no-train-step"])):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--latent", "32", "--refs", "6",
+               "--fp8-attn", "--dump-outputs", str(tmp_path / run)] + extra
+        res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert res.returncode == 0, res.stderr[-3000:]
+        out = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, res.stdout[-2000:]
+        lines[run] = json.loads(out[0])
+    plain, full = lines["plain"], lines["full"]
+    for line in (plain, full):
+        assert line["unit"] == "steps/s" and line["higher_is_better"] is True and line["dtype"] == "bf16" and line["steps"] == 2 and line["warmup"] == 1
+        assert line["value"] > 0 and abs(line["value"] - 1e3 / line["ms_per_step"]) < 1e-2 * line["value"]
+        assert line["config"]["render_step_ms"] > 0 and line["config"]["steady_step_ms"] > 0
+    assert plain["metric"] == full["metric"] and set(plain) <= set(full)
+    assert plain["roofline"] is None and plain["rooflines"] == {} and plain["config"]["kernel_ms_per_step"] == {}
+    for key in ("cpu_baseline", "train_step", "fp8_tolerance"):
+        assert key not in plain, key
+    assert "reference_tables_ms" not in plain["config"]
+    assert full["roofline"]["kernel"] in full["config"]["kernel_ms_per_step"] and full["rooflines"] and full["config"]["reference_tables_ms"] >= 0
+    assert full["cpu_baseline"]["value"] > 0 and full["fp8_tolerance"]["rendered_feat_max_rel"] >= 0 and "train_step" not in full
+    a, b = np.load(tmp_path / "plain" / "latents.npy"), np.load(tmp_path / "full" / "latents.npy")
+    assert a.shape == (1, 4, 32, 32) and np.isfinite(a).all() and a.std() > 0
+    assert np.allclose(a, b, rtol=0, atol=1e-5 * float(np.abs(a).max())), float(np.abs(a - b).max())

@@ -4,7 +4,7 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 for V in "$@"; do
   if [ "$V" = "-" ]; then V=""; fi
   echo "== variant: [$V]"
-  env $V python bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 | python -c "
+  env $V python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('steps/s', d['value'], 'steady_ms', d['config']['steady_step_ms'], 'render_ms', d['config']['render_step_ms'])

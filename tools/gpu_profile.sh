@@ -21,4 +21,4 @@ for C in FETCH_SIZE WRITE_SIZE; do
   cat $OUT/pmc_$C.csv
 done
 cd $GRAFT_REPO_ROOT
-if [ "$3" == "bench" ]; then timeout 900 python bench.py --steps 50 --warmup 3 > gpurun_out/bench_$TAG.log 2>&1; echo "bench exit $?"; tail -1 gpurun_out/bench_$TAG.log; fi
+if [ "$3" == "bench" ]; then timeout 900 python bench.py --full --steps 50 --warmup 3 > $OUT/../bench_$TAG.log 2>&1; echo "bench exit $?"; tail -1 $OUT/../bench_$TAG.log; fi
