@@ -33,6 +33,10 @@ class Sampler:
     not reset between images: `step(x, i)` for i > 0 must follow `step(., i - 1)` of the SAME image (`eps()` is unaffected).
     A solver that draws noise draws it INSIDE its kernels as a pure function of (`seed`, the row's noise stream, step index, channel, pixel)
     (include/cd360_stochastic.h), so graph, eager, fresh and un-staged runs add the same bits and no state is kept between steps.
+    `discretization` / `sigmas`: the sigma schedule -- an object with LegacyDDPMDiscretization's call protocol (cd360.sampler:
+    EDMDiscretization, the Karras rho schedule; ListDiscretization), or the `n_steps` values themselves; neither: the legacy schedule.
+    Where a schedule leaves the denoiser's 1000-entry grid (`on_grid` False) the network runs at the snapped sigma and the solver steps
+    on the schedule's own: "euler", "heun" and "dpmpp2m" serve that (solvers.select), the other solvers refuse it with a ValueError.
     `noise_streams`: one id per replay row (default: stream 0 everywhere -- all poses of a job share the injected noise, as
     sample.py:290-292 shares the start noise); `reseed` / `set_noise_streams` rewrite the device buffers, no re-capture."""
 
@@ -41,13 +45,20 @@ class Sampler:
     HIGHORDER_SOLVERS = tuple(solvers.HIGHORDER_SOLVERS)
 
     def __init__(self, net, pose, ctx, y, n_steps, scale=7.5, scale_im=3.5, use_graph=False, prefetch=None, graph_render=True, solver="euler",
-                 eta=1.0, s_noise=1.0, seed=0, noise_streams=None, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), order=4):
+                 eta=1.0, s_noise=1.0, seed=0, noise_streams=None, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), order=4, discretization=None,
+                 sigmas=None):
         from cd360 import sampler as S
         if solver not in solvers.NAMES:
             raise ValueError(f"solver {solver!r}: the job sampler serves {', '.join(solvers.NAMES)}")
         if solver == "lms" and (isinstance(order, bool) or not isinstance(order, int) or not 1 <= order <= 4):
             raise ValueError(f"order {order!r}: the linear multistep solver serves orders 1..4")
-        self.solver, self._solver, self.order = solver, solvers.select(solver, s_churn), order  # the name, and what only that solver knows
+        if discretization is not None and sigmas is not None:
+            raise ValueError("give `discretization` or `sigmas`, not both")
+        if sigmas is not None:
+            if len(sigmas) != n_steps:
+                raise ValueError(f"{len(sigmas)} sigmas for n_steps = {n_steps}")
+            discretization = S.ListDiscretization(sigmas)
+        self.solver, self.order = solver, order
         self.eta, self.s_noise, self.seed, self.noise_streams = eta, s_noise, seed, noise_streams
         self.s_churn, self.s_tmin, self.s_tmax = s_churn, s_tmin, s_tmax
         self.last_row = False  # True while the step at hand is a one-evaluation row of a two-evaluation solver (Solver.single_row)
@@ -67,7 +78,14 @@ class Sampler:
         if ctx.shape[0] % nb or y.shape[0] != ctx.shape[0] or (isinstance(pose, (list, tuple)) and len(pose) != ctx.shape[0]):
             raise ValueError(f"the {nb}-branch guider takes ctx / y / pose of {nb} x bs rows, got {ctx.shape[0]} / {y.shape[0]} / "
                              f"{len(pose) if isinstance(pose, (list, tuple)) else '?'}")
-        self.sigmas = S.LegacyDDPMDiscretization()(n_steps, device=dev)  # n_steps + 1 values, last = 0
+        # n_steps + 1 values, last = 0: the legacy schedule unless the caller names another (cd360.sampler: EDMDiscretization,
+        # ListDiscretization, or anything with their call protocol)
+        disc = S.LegacyDDPMDiscretization() if discretization is None else discretization
+        self.sigmas = disc(n_steps, device=dev)
+        # once per schedule, on the host's own evaluation of it (no step reads anything back): the denoiser's table is the host's evaluation
+        # of the legacy schedule, and the device's square root may differ from it in the last bit -- which moves no sigma off the grid
+        self.on_grid = S.on_grid(disc(n_steps), self.denoiser)
+        self._solver = solvers.select(solver, s_churn, self.on_grid)  # what only that solver knows (off the grid: or a ValueError)
         # conditioning is constant over a trajectory: the guider's (uc, uc, c) / (uc, c) batch is assembled once per image, not per step
         self.bs = bs = ctx.shape[0] // nb  # diffusion samples (target poses) per replay: ctx / y hold [uc x bs | . | c x bs] / [uc x bs | c x bs]
         cond3 = self._cond_batch(ctx, y)
@@ -135,16 +153,10 @@ class Sampler:
     def _build_stage(self, x):
         """Per-schedule tables and static buffers of the staged steps: row i = what step i of the trajectory derives from sigma_i alone,
         computed with the denoiser's / the UNet's own modules exactly as the un-staged step computes them inside its graph."""
+        self.step_tab, sqs = self.step_table()  # (before the solver's own tables: one of them may be this table with a column replaced)
         self._build_state(x)
         net, dev, dt = self.net, x.device, self.net.dtype
-        rows, sqs = [], []
-        for i in range(self.n_steps):
-            sq = self.denoiser.possibly_quantize_sigma(self.sigmas[i].reshape(1))
-            c_in = self.denoiser.scaling(sq)[2]
-            rows.append(torch.stack([self.sigmas[i], self.sigmas[i + 1], c_in[0], torch.zeros_like(c_in[0])]))
-            sqs.append(sq[0])
-        self.step_tab = torch.stack(rows).float().contiguous()
-        self.temb_tab = self.temb_rows(torch.stack(sqs))
+        self.temb_tab = self.temb_rows(sqs)
         conv = net.input_blocks[0][0]
         self.w36 = conv.weight.detach().float().permute(2, 3, 1, 0).reshape(36, conv.out_channels).contiguous()
         self.b_in = (conv.bias.detach().float() if conv.bias is not None else torch.zeros(conv.out_channels, device=dev)).contiguous()
@@ -153,6 +165,18 @@ class Sampler:
         self.h0 = torch.empty(nbs, H * W, conv.out_channels, dtype=dt, device=dev)
         self.emb_act = torch.empty_like(self.lab)
         self._solver.build_stage(self)
+
+    @torch.no_grad()
+    def step_table(self):
+        """(step_tab [n, 4] fp32 = (sigma_i, sigma_next, c_in(q_i), 0), q [n]) with q_i = the denoiser's snap of sigma_i, c_in through the
+        denoiser's own module on the device."""
+        rows, sqs = [], []
+        for i in range(self.n_steps):
+            sq = self.denoiser.possibly_quantize_sigma(self.sigmas[i].reshape(1))
+            c_in = self.denoiser.scaling(sq)[2]
+            rows.append(torch.stack([self.sigmas[i], self.sigmas[i + 1], c_in[0], torch.zeros_like(c_in[0])]))
+            sqs.append(sq[0])
+        return torch.stack(rows).float().contiguous(), torch.stack(sqs)
 
     @torch.no_grad()
     def temb_rows(self, sq):

@@ -48,6 +48,52 @@ class LegacyDDPMDiscretization:
         return sigmas if not flip else torch.flip(sigmas, (0,))
 
 
+class EDMDiscretization:
+    """The Karras rho schedule, sigma_i = (sigma_max^(1/rho) + i / (n - 1) (sigma_min^(1/rho) - sigma_max^(1/rho)))^rho
+    (discretizer.py:28-39): the reference's expression in the reference's order, in fp32 on `device`.  Its values lie OFF the 1000-entry
+    table DiscreteDenoiser snaps to (on_grid, below): the network then runs at the snapped sigma, the solver on the schedule's own."""
+
+    def __init__(self, sigma_min=0.002, sigma_max=80.0, rho=7.0):
+        self.sigma_min, self.sigma_max, self.rho = sigma_min, sigma_max, rho
+
+    __call__ = LegacyDDPMDiscretization.__call__  # the call protocol every discretisation shares (discretizer.py:17-21)
+
+    def get_sigmas(self, n, device="cpu"):
+        ramp = torch.linspace(0, 1, n, device=device)
+        min_inv_rho = self.sigma_min ** (1 / self.rho)
+        max_inv_rho = self.sigma_max ** (1 / self.rho)
+        return (max_inv_rho + ramp * (min_inv_rho - max_inv_rho)) ** self.rho
+
+
+class ListDiscretization:
+    """A caller's own schedule (a published few-step list): `sigmas` strictly decreasing and positive, handed back as fp32 for exactly
+    n = len(sigmas); the zero is appended as by the other discretisations."""
+
+    def __init__(self, sigmas):
+        vals = [float(v) for v in (sigmas.detach().cpu().reshape(-1).tolist() if isinstance(sigmas, torch.Tensor) else sigmas)]
+        if not vals or not all(v > 0 and v < float("inf") for v in vals):
+            raise ValueError(f"a sigma list holds positive finite values, got {vals}")
+        self.sigmas = torch.tensor(vals, dtype=torch.float32)
+        if not bool((self.sigmas[1:] < self.sigmas[:-1]).all()):  # (compared as the fp32 values the steps will use)
+            raise ValueError(f"a sigma list is strictly decreasing, got {vals}")
+
+    __call__ = LegacyDDPMDiscretization.__call__
+
+    def get_sigmas(self, n, device="cpu"):
+        if n != self.sigmas.numel():
+            raise ValueError(f"this list holds {self.sigmas.numel()} sigmas; asked for {n}")
+        return self.sigmas.to(device)
+
+
+def on_grid(sigmas: torch.Tensor, denoiser: "DiscreteDenoiser") -> bool:
+    """Does every non-zero entry of `sigmas` lie ON the denoiser's table, possibly_quantize_sigma(s) == s?  Then c_out, c_in and the time
+    embedding (from the snapped sigma) and to_d / dt / the multistep coefficients (from the schedule's own) read one scalar per step, as on
+    LegacyDDPMDiscretization; otherwise a step needs both.  Decided once per schedule, in CPU fp32 whatever device the two live on."""
+    sig = sigmas.detach().to("cpu", torch.float32).reshape(-1)
+    sig = sig[sig != 0]
+    return bool(torch.equal(snap_c_in(denoiser, denoiser.sigmas.detach().to("cpu", torch.float32), sig)[1], sig))
+
+
 # ----------------------------------------------------------------------------------------------- denoiser
 class EpsScaling:
     def __call__(self, sigma):
@@ -462,14 +508,28 @@ def cfg_dpmpp2m_update(x: torch.Tensor, eps: torch.Tensor, old: Optional[torch.T
     return m1 * x - m2 * dd, d0
 
 
+def dpmpp2m_cout_table(step_tab: torch.Tensor, sigmas: torch.Tensor, denoiser: "DiscreteDenoiser", grid: Optional[bool] = None) -> torch.Tensor:
+    """The table the DPM++ 2M tail takes in place of step_tab [n, 4] = (sigma_i, sigma_next, c_in(q_i), 0): the tail reads column 0 for
+    c_out ALONE (everything else comes from dpmpp2m_multipliers, built from the schedule's own sigmas), so column 0 becomes q_i =
+    denoiser.possibly_quantize_sigma(sigma_i) and columns 1..3 stay.  On a schedule that lies on the denoiser's grid (`grid`; None: asked
+    of on_grid) q_i is sigma_i and the result is `step_tab` ITSELF: the same object, the same launch."""
+    if on_grid(sigmas, denoiser) if grid is None else grid:
+        return step_tab
+    tab = step_tab.clone()
+    tab[:, 0] = denoiser.possibly_quantize_sigma(sigmas[:-1].to(denoiser.sigmas.device)).to(tab.device, tab.dtype)
+    return tab.contiguous()
+
+
 def fused_cfg_dpmpp2m_step(denoiser: "DiscreteDenoiser", network: Callable, x: torch.Tensor, old: Optional[torch.Tensor], sigma: torch.Tensor,
-                           mult: torch.Tensor, guider, fused: bool = True):
+                           mult: torch.Tensor, guider, fused: bool = True, sigma_q: Optional[torch.Tensor] = None):
     """ONE step of DPMPP2MSampler.sampler_step (sampling.py:413-445) in the form the sampling job launches it: fused_cfg_euler_step with the
     tail replaced -- x' , d0 = cfg_dpmpp2m_update(x, eps, old, sigma, mult): cd360_cfg_dpmpp2m_step_f32.  `mult` = row i of
-    dpmpp2m_multipliers(sigmas) for sigma = sigmas[i]; `old` = the d0 step i - 1 returned.  Returns (x', d0)."""
+    dpmpp2m_multipliers(sigmas) for sigma = sigmas[i]; `old` = the d0 step i - 1 returned.  Returns (x', d0).
+    `sigma_q`: the tail's only scalar is c_out's, the SNAPPED sigma; off the denoiser's grid the caller passes it (a device tensor holding
+    possibly_quantize_sigma(sigma): nothing is read back), on the grid it is `sigma`."""
     scale, scale_im = guider_scales(guider)
     eps = cfg_eps(denoiser, network, x, sigma, guider.branches)
-    return cfg_dpmpp2m_update(x, eps.contiguous(), old, sigma.reshape(1), mult, scale, scale_im, fused=fused)
+    return cfg_dpmpp2m_update(x, eps.contiguous(), old, (sigma if sigma_q is None else sigma_q).reshape(1), mult, scale, scale_im, fused=fused)
 
 
 # ----------------------------------------------------------------------------------------------- ancestral Euler

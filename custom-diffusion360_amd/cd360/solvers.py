@@ -2,7 +2,8 @@
 route copies per step (`rows`), the tail kernel that ends a staged step, its un-staged step, and whether it draws noise.  One stateless
 object per solver; the state lives on the Sampler `smp` they are handed, under the names tests and tools read, next to the buffers every
 solver shares (smp.gx, smp.gi, smp._iota, smp.step_tab).  SOLVERS holds the one-evaluation solvers on the step table, EDM_SOLVERS the EDM
-family (include/cd360_edm.h), HIGHORDER_SOLVERS DPM++ 2S ancestral and linear multistep (include/cd360_highorder.h); select() picks."""
+family (include/cd360_edm.h), HIGHORDER_SOLVERS DPM++ 2S ancestral and linear multistep (include/cd360_highorder.h); select() picks, by
+the name, the churn and whether the schedule lies on the denoiser's grid."""
 from __future__ import annotations
 
 import torch
@@ -33,9 +34,13 @@ class Solver:
     def tables(self, smp, x):
         """The solver's per-schedule tables and the buffers it carries, on x's device."""
 
+    def rows_of(self, smp):
+        """`rows` for this sampler's schedule."""
+        return self.rows
+
     def build(self, smp, x):
         self.tables(smp, x)
-        for buf, tab in self.rows:
+        for buf, tab in self.rows_of(smp):
             if (buf, tab) != GI:
                 setattr(smp, buf, getattr(smp, tab)[0].clone())
 
@@ -43,7 +48,7 @@ class Solver:
         """Staged route only, after the sampler's own tables exist: further stage-in tables."""
 
     def set_row(self, smp, i):
-        for buf, tab in self.rows:  # in the order declared
+        for buf, tab in self.rows_of(smp):  # in the order declared
             getattr(smp, buf).copy_(getattr(smp, tab)[i:i + 1] if (buf, tab) == GI else getattr(smp, tab)[i])
 
     def staged_step(self, smp, evaluate):
@@ -79,9 +84,15 @@ class Euler(Solver):
 
 
 class DPMPP2M(Solver):
-    """DPMPP2MSampler (sampling.py:390-465: second order, multistep, the same one UNet evaluation per step)."""
+    """DPMPP2MSampler (sampling.py:390-465: second order, multistep, the same one UNet evaluation per step).  Off the denoiser's grid
+    (smp.on_grid False) the tail's one scalar, c_out's, is the SNAPPED sigma: the staged tail takes smp.cout_tab in place of smp.step_tab,
+    the un-staged one the row in smp.gq; the multipliers come from the schedule's own sigmas either way."""
 
     rows = (("gm", "mult_tab"),)
+    off_grid_rows = rows + (("gq", "cout_tab"),)  # un-staged, off the grid: the step's row of cout_tab, whose element 0 is q(sigma_i)
+
+    def rows_of(self, smp):
+        return self.rows if smp.on_grid else self.off_grid_rows
 
     def tables(self, smp, x):
         """The multiplier table (host fp32, uploaded: the same bits in every sampler of a schedule) and gd = the previous step's denoised
@@ -89,12 +100,18 @@ class DPMPP2M(Solver):
         kernels then never read it -- which is also why step(x, i) for i > 0 must follow step(., i - 1) of the same image."""
         smp.mult_tab = S.dpmpp2m_multipliers(smp.sigmas).to(x.device)
         smp.gd = torch.zeros_like(x)
+        # cout_tab: step_tab with column 0 = q(sigma_i) -- on the grid step_tab ITSELF.  The staged sampler built step_tab before its
+        # solver's tables; the un-staged route has none and reads cout_tab off the grid alone (rows_of)
+        step_tab = getattr(smp, "step_tab", None)
+        if step_tab is None and not smp.on_grid:
+            step_tab = smp.step_table()[0]
+        smp.cout_tab = None if step_tab is None else S.dpmpp2m_cout_table(step_tab, smp.sigmas, smp.denoiser, smp.on_grid)
 
-    def tail(self, smp, eps_cl):  # x and gd in place: [c_out, CFG, multistep update]
-        return ops.cfg_dpmpp2m_step_cl(smp.gx, smp.gd, eps_cl, smp.step_tab, smp.mult_tab, smp.gi, smp.scale, smp.scale_im)
+    def tail(self, smp, eps_cl):  # x and gd in place: [c_out at q(sigma), CFG, multistep update]
+        return ops.cfg_dpmpp2m_step_cl(smp.gx, smp.gd, eps_cl, smp.cout_tab, smp.mult_tab, smp.gi, smp.scale, smp.scale_im)
 
-    def step(self, smp, unet, x, s, s_next):  # the kernel on the row in gm; this step's d0 moves into gd
-        out, d0 = S.fused_cfg_dpmpp2m_step(smp.denoiser, unet, x, smp.gd, s, smp.gm, smp.guider)
+    def step(self, smp, unet, x, s, s_next):  # the kernel on the row in gm (off the grid: c_out's sigma in gq); this step's d0 moves into gd
+        out, d0 = S.fused_cfg_dpmpp2m_step(smp.denoiser, unet, x, smp.gd, s, smp.gm, smp.guider, sigma_q=None if smp.on_grid else smp.gq[:1])
         smp.gd.copy_(d0)
         return out
 
@@ -256,8 +273,16 @@ HIGHORDER_SOLVERS = {"dpmpp2s_a": DPMPP2SAncestral(), "lms": LMS()}
 NAMES = tuple(SOLVERS) + tuple(k for k in EDM_SOLVERS if k not in SOLVERS) + tuple(HIGHORDER_SOLVERS)  # every solver name, once
 
 
-def select(name, s_churn=0.0) -> Solver:
-    """The object that serves `name`.  A name two registries share ("euler") is the EDM family's as soon as the schedule churns, and
-    SOLVERS' own otherwise (kernels and launch count of the un-churned step unchanged)."""
-    edm = name in EDM_SOLVERS and (name not in SOLVERS or s_churn > 0)
+OFF_GRID = ("euler", "heun", "dpmpp2m")  # the solvers whose kernels take the snapped sigma (c_out) and the schedule's own (to_d, dt) apart
+
+
+def select(name, s_churn=0.0, on_grid=True) -> Solver:
+    """The object that serves `name`.  A name two registries share ("euler") is the EDM family's as soon as the schedule churns or leaves
+    the denoiser's grid (cd360.sampler.on_grid: its tables hold sigma_hat and the snapped sigma side by side; with gamma = 0 no churn
+    kernel runs), and SOLVERS' own otherwise (kernels and launch count of the un-churned on-grid step unchanged).  The tails of the
+    remaining solvers read ONE sigma for c_out and for to_d: off the grid they are refused."""
+    if not on_grid and name not in OFF_GRID:
+        raise ValueError(f"solver {name!r} reads one sigma per step for c_out and to_d, and this schedule does not lie on the denoiser's grid "
+                         f"(a Karras or listed schedule): off the grid the job sampler serves {', '.join(OFF_GRID)}")
+    edm = name in EDM_SOLVERS and (name not in SOLVERS or s_churn > 0 or not on_grid)
     return (EDM_SOLVERS if edm else HIGHORDER_SOLVERS if name in HIGHORDER_SOLVERS else SOLVERS)[name]

@@ -8,6 +8,9 @@ further solvers.  Calls the job sampler directly (bench.py keeps measuring the E
   --order                  the order of LinearMultistepSampler's constructor, for --solver lms (default 4)
   --s-churn / --s-tmin / --s-tmax / --s-noise   the churn of EDMSampler's constructor, for --solver euler and heun (default: none)
   --branches 2|3           which guider
+  --schedule legacy|karras:<min>:<max>:<rho>|list:<v,v,...>   the sigma schedule of BOTH routes (default legacy: LegacyDDPMDiscretization, also
+                           on a checkout that predates the option); karras = EDMDiscretization, list = ListDiscretization (n_steps values).
+                           Off the denoiser's grid the job serves --solver euler, heun and dpmpp2m
   --what deviation         n_steps = 4, all 4 steps at latent 32 / 6 views: the captured job sampler against the un-captured module route
                            (cd360.sampler's EulerEDMSampler / DPMPP2MSampler / EulerAncestralSampler / HeunEDMSampler / DPMPP2SAncestralSampler /
                            LinearMultistepSampler + the guider + DiscreteDenoiser around the same UNet, eager),
@@ -36,6 +39,7 @@ ap.add_argument("--s-tmin", type=float, default=0.0)
 ap.add_argument("--s-tmax", type=float, default=float("inf"))
 ap.add_argument("--s-noise", type=float, default=1.0)
 ap.add_argument("--branches", type=int, default=3, choices=(2, 3))
+ap.add_argument("--schedule", default="legacy")
 ap.add_argument("--what", default="deviation", choices=("deviation", "timing"))
 ap.add_argument("--repo", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--latent", type=int, default=128)
@@ -56,6 +60,28 @@ CHURN = dict(s_churn=args.s_churn, s_tmin=args.s_tmin, s_tmax=args.s_tmax, s_noi
 if CHURN and args.solver not in ("euler", "heun"):
     ap.error("--s-churn applies to --solver euler and heun")
 LABEL = args.solver + ("_churn" if CHURN else "")
+
+
+def schedule():
+    """--schedule -> (the discretisation object for job.Sampler, the discretization_config of the un-captured classes); (None, None): legacy."""
+    kind, _, rest = args.schedule.partition(":")
+    try:
+        if kind == "legacy" and not rest:
+            return None, None
+        if kind == "karras":
+            lo, hi, rho = (float(v) for v in rest.split(":"))
+            params = {"sigma_min": lo, "sigma_max": hi, "rho": rho}
+            return S.EDMDiscretization(**params), {"target": "sgm.modules.diffusionmodules.discretizer.EDMDiscretization", "params": params}
+        if kind == "list":
+            vals = [float(v) for v in rest.split(",")]
+            return S.ListDiscretization(vals), {"target": "sgm.modules.diffusionmodules.discretizer.ListDiscretization", "params": {"sigmas": vals}}
+    except ValueError as e:
+        ap.error(f"--schedule {args.schedule}: {e}")
+    ap.error("--schedule takes legacy, karras:<min>:<max>:<rho> or list:<v,v,...>")
+
+
+DISC, DISC_CFG = schedule()
+SCHED = {} if DISC_CFG is None else {"discretization_config": DISC_CFG}  # (for the un-captured classes)
 
 
 def one_pose(p, latent, refs):
@@ -81,6 +107,8 @@ def make(net, pose, ctx, y, n_steps, solver, churn=None):
     if solver == "lms":
         kw["order"] = args.order
     kw.update(churn or {})
+    if DISC is not None:
+        kw["discretization"] = DISC
     return job.Sampler(net, pose, ctx, y, n_steps, scale_im=SCALE_IM, use_graph=True, **kw)
 
 
@@ -99,13 +127,13 @@ def deviation():
             {"target": "sgm.modules.diffusionmodules.guiders.ScheduledCFGImgTextRef", "params": {"scale": 7.5, "scale_im": 3.5}})
     if args.solver in ("euler_a", "dpmpp2s_a"):
         cls = S.EulerAncestralSampler if args.solver == "euler_a" else S.DPMPP2SAncestralSampler
-        mod = cls(eta=args.eta, num_steps=steps, guider_config=gcfg, device=DEV, seed=SEED)
+        mod = cls(eta=args.eta, num_steps=steps, guider_config=gcfg, device=DEV, seed=SEED, **SCHED)
     elif args.solver == "lms":
-        mod = S.LinearMultistepSampler(order=args.order, num_steps=steps, guider_config=gcfg, device=DEV)
+        mod = S.LinearMultistepSampler(order=args.order, num_steps=steps, guider_config=gcfg, device=DEV, **SCHED)
     elif args.solver == "heun" or CHURN:
-        mod = (S.HeunEDMSampler if args.solver == "heun" else S.EulerEDMSampler)(num_steps=steps, guider_config=gcfg, device=DEV, seed=SEED, **CHURN)
+        mod = (S.HeunEDMSampler if args.solver == "heun" else S.EulerEDMSampler)(num_steps=steps, guider_config=gcfg, device=DEV, seed=SEED, **CHURN, **SCHED)
     else:
-        mod = (S.EulerEDMSampler if args.solver == "euler" else S.DPMPP2MSampler)(num_steps=steps, guider_config=gcfg, device=DEV)
+        mod = (S.EulerEDMSampler if args.solver == "euler" else S.DPMPP2MSampler)(num_steps=steps, guider_config=gcfg, device=DEV, **SCHED)
     den = S.DiscreteDenoiser().to(DEV)
     sampling.set_cfg_branches(net, NB)
     sampling.clear_rendered_feat(net)
@@ -128,7 +156,7 @@ def deviation():
         else:
             x, old = mod.sampler_step(old, None if i == 0 else sig[i - 1].reshape(1), s, sn, denoiser, x, c, uc)
     sampling.clear_rendered_feat(net)
-    out(figure="job_vs_module_route", solver=LABEL, n_steps=steps, steps=steps, max_abs=float((got - x).abs().max()),
+    out(figure="job_vs_module_route", solver=LABEL, schedule=args.schedule, on_grid=bool(getattr(smp, "on_grid", True)), n_steps=steps, steps=steps, max_abs=float((got - x).abs().max()),
         rel=float((got - x).abs().max() / x.abs().max()), latent_max=float(x.abs().max()), staged=bool(smp.staged))
 
 
