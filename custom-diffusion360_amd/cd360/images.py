@@ -12,7 +12,14 @@ reference's two 1 x 1 `nn.Conv2d` modules `quant_conv` / `post_quant_conv`, whos
 
 The posterior's noise is a pure function of (seed, streams[image], draw, channel, pixel), not of torch's generator: `draw` is the training
 step (or any call count), so successive samples of one image differ, and a re-run of a step reproduces its latents on any rank layout.
-Forward only, under no_grad; a CPU tensor raises."""
+Forward only, under no_grad; a CPU tensor raises.
+
+Keeping part of a picture, or starting from one (masked and image-to-image sampling):
+
+  known = first_stage.encode_mode(picture)                  [P, 4, h, w]: the latents of the pictures to keep / to start from
+  masks = latent_mask(region)                               [P, 1, h, w]: 1 = generate, 0 = keep, from an image-resolution mask
+  job.sample_images(..., init_latents=known, masks=masks)   keeps the picture outside the region, synthesises inside it
+  job.sample_images(..., init_latents=known, masks=masks, first_step=k, latent_hw=(h, w))   and runs only rows k.. of the schedule"""
 from __future__ import annotations
 
 import torch
@@ -33,6 +40,21 @@ def _conv1x1_pack(conv: nn.Conv2d, n_out: int, n_in: int):
         b = conv.bias.detach().float().contiguous() if conv.bias is not None else torch.zeros(n_out, dtype=torch.float32, device=w.device)
         return w, b
     return derived(conv, "_cd360_pack", (conv.weight, conv.bias), make)
+
+
+def latent_mask(mask: torch.Tensor, factor: int = 8) -> torch.Tensor:
+    """An image-resolution mask [N, 1, H, W] or [N, H, W] (bool / uint8 / float; nonzero resp. 1 = generate) -> the mask of the latent's
+    pixels [N, 1, H / factor, W / factor] fp32: the area average, so a latent pixel on the region's border blends in proportion.  torch,
+    once per image, outside the step; H and W must be multiples of `factor` (the first stage's down-sampling)."""
+    if not isinstance(mask, torch.Tensor) or mask.ndim not in (3, 4) or (mask.ndim == 4 and mask.shape[1] != 1):
+        raise ValueError(f"mask: [N, 1, H, W] or [N, H, W] is needed, got {tuple(getattr(mask, 'shape', ()))}")
+    if mask.ndim == 3:
+        mask = mask[:, None]
+    H, W = mask.shape[2:]
+    if factor <= 0 or H % factor or W % factor or H * W == 0:
+        raise ValueError(f"mask of {H} x {W}: both must be positive multiples of factor = {factor}")
+    m = (mask != 0) if mask.dtype in (torch.bool, torch.uint8) else mask
+    return torch.nn.functional.avg_pool2d(m.float(), factor).contiguous()
 
 
 class FirstStage:

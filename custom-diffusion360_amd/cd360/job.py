@@ -8,6 +8,8 @@ at the next pose by `Sampler.retarget` (camera buffer and conditioning rewritten
 `shard.gather_latents` collects the final latents (RCCL all-gather over xGMI; gloo in the CPU tests).  `bench.py` times exactly this loop.
 `sample_images` is the same job from a seed to uint8 images: the start latent drawn on the device (`start_latent`), every rank decoding its
 own poses through the first stage (cd360/images.py), and the one all-gather moving the images instead of the latents.
+A `Sampler` built with `known` / `mask` keeps a given latent outside a region (one more launch per step, include/edit/cd360_edit.h);
+`start_from` and `first_step` run only the tail of the schedule from a given latent.
 """
 from __future__ import annotations
 
@@ -17,6 +19,34 @@ from typing import Callable, List, Sequence
 import torch
 
 from . import shard, solvers
+
+
+def check_known(bs: int, known, mask, latent_shape=None) -> None:
+    """What a masked Sampler asks of (known, mask), on the host and before anything is launched: both or neither; known [bs or 1, 4, H, W]
+    and mask [bs or 1, 1, H, W] fp32 tensors of one H x W -- that of `latent_shape` = (bs, 4, H, W) once the latent has been seen."""
+    if (known is None) != (mask is None):
+        raise ValueError("`known` and `mask` go together: the latent to keep and the region (1 = generate, 0 = keep); give both or neither")
+    if known is None:
+        return
+    if not isinstance(known, torch.Tensor) or known.dtype != torch.float32 or known.ndim != 4 or known.shape[1] != 4 or known.shape[0] not in (1, bs):
+        raise ValueError(f"known: an fp32 tensor [{bs} or 1, 4, H, W] is needed, got {getattr(known, 'dtype', type(known))} "
+                         f"{tuple(getattr(known, 'shape', ()))}")
+    want = (1,) + tuple(known.shape[2:])
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.float32 or mask.ndim != 4 or tuple(mask.shape[1:]) != want or mask.shape[0] not in (1, bs):
+        raise ValueError(f"mask: an fp32 tensor [{bs} or 1, 1, {want[1]}, {want[2]}] at latent resolution is needed, got "
+                         f"{getattr(mask, 'dtype', type(mask))} {tuple(getattr(mask, 'shape', ()))}")
+    if latent_shape is not None and tuple(known.shape[2:]) != tuple(latent_shape[2:]):
+        raise ValueError(f"known is {tuple(known.shape[2:])}, the latent {tuple(latent_shape[2:])}")
+
+
+def check_first_step(solver, first_step: int, n_steps: int) -> None:
+    """A trajectory that begins at row `first_step` of an `n_steps` schedule: rows 0 .. n_steps - 1, and past row 0 only under the solvers
+    whose kernels do not key "no history yet" on row 0 (Sampler.PARTIAL_START).  `solver`: the name, or None for a sampler without one."""
+    if isinstance(first_step, bool) or not isinstance(first_step, int) or not 0 <= first_step < n_steps:
+        raise ValueError(f"first_step {first_step!r}: a row 0 .. {n_steps - 1} of the {n_steps}-step schedule is needed")
+    if first_step > 0 and solver is not None and solver not in Sampler.PARTIAL_START:
+        raise ValueError(f"solver {solver!r} keeps earlier steps' results and reads none of them on row 0 only: a trajectory cannot begin at row "
+                         f"{first_step}.  Partial starts are served by 'euler' (with and without churn), 'heun', 'euler_a' and 'dpmpp2s_a'")
 
 
 class Sampler:
@@ -38,7 +68,19 @@ class Sampler:
     Where a schedule leaves the denoiser's 1000-entry grid (`on_grid` False) the network runs at the snapped sigma and the solver steps
     on the schedule's own: "euler", "heun" and "dpmpp2m" serve that (solvers.select), the other solvers refuse it with a ValueError.
     `noise_streams`: one id per replay row (default: stream 0 everywhere -- all poses of a job share the injected noise, as
-    sample.py:290-292 shares the start noise); `reseed` / `set_noise_streams` rewrite the device buffers, no re-capture."""
+    sample.py:290-292 shares the start noise); `reseed` / `set_noise_streams` rewrite the device buffers, no re-capture.
+    `known` / `mask` (both or neither): masked sampling.  known [bs, 4, H, W] fp32 = the latent to keep, mask [bs or 1, 1, H, W] fp32 at latent
+    resolution, 1 = generate, 0 = keep.  Every step then ends in ONE more launch, after the solver's whole step (never between a solver's
+    two evaluations): the region to keep is replaced by `known` at the step's new noise level (cd360_mask_blend_f32 of
+    include/edit/cd360_edit.h, captured inside all three graphs; its noise is counter domain 3 under `seed` and the rows' streams, so such
+    a sampler owns the seed / stream buffers and `reseed` / `set_noise_streams` serve it under a deterministic solver as well).  Both live
+    in buffers the sampler owns: `set_known` rewrites them in place, no re-capture.  Without them the step is what it was: no buffer,
+    launch or graph node is added.
+    `step(x, i, first=True)` makes row i the first step of an image (the render runs there): with `start_from` the tail of a schedule from a
+    given picture, image-to-image.  The solvers of PARTIAL_START serve it."""
+
+    # a trajectory may begin at a row > 0 under these: "dpmpp2m" and "lms" key "no history yet" on row 0 of their tables
+    PARTIAL_START = ("euler", "heun", "euler_a", "dpmpp2s_a")
 
     SOLVERS = tuple(solvers.SOLVERS)
     EDM_SOLVERS = tuple(k for k in solvers.EDM_SOLVERS if k not in solvers.SOLVERS)  # the names only the EDM registry serves
@@ -46,7 +88,7 @@ class Sampler:
 
     def __init__(self, net, pose, ctx, y, n_steps, scale=7.5, scale_im=3.5, use_graph=False, prefetch=None, graph_render=True, solver="euler",
                  eta=1.0, s_noise=1.0, seed=0, noise_streams=None, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), order=4, discretization=None,
-                 sigmas=None):
+                 sigmas=None, known=None, mask=None):
         from cd360 import sampler as S
         if solver not in solvers.NAMES:
             raise ValueError(f"solver {solver!r}: the job sampler serves {', '.join(solvers.NAMES)}")
@@ -99,6 +141,10 @@ class Sampler:
         # eager launches (use_graph=False) run the same staged step
         from cd360 import routes
         self.staged = bool(not routes.no_stage and self._stageable())
+        check_known(self.bs, known, mask)
+        self.masked = known is not None  # decided once: the captured graphs hold the blend or they do not
+        self.known_buf = self.mask_buf = None  # _build_state, on the first step; until then the caller's tensors wait here
+        self._known = (known, mask)
         self._state_layout()
 
     def _state_layout(self):
@@ -148,6 +194,14 @@ class Sampler:
         self._iota = torch.arange(self.n_steps, dtype=torch.int32, device=x.device)
         self.gi = torch.zeros(1, dtype=torch.int32, device=x.device)
         self._solver.build(self, x)
+        if self.masked:
+            known, mask = self._known
+            check_known(self.bs, known, mask, tuple(x.shape))
+            self.known_buf = known.to(x.device).expand(x.shape).contiguous().clone()
+            self.mask_buf = mask.to(x.device).contiguous().clone()
+            self._known = None
+            if not self._solver.draws(self):  # a masked sampler draws the kept region's noise even under a deterministic solver
+                solvers.Solver.noise_buffers(self, x)
 
     @torch.no_grad()
     def _build_stage(self, x):
@@ -190,8 +244,31 @@ class Sampler:
             tembs.append(net.time_embed(timestep_embedding(c_noise.expand(self.branches), net.model_channels).to(dt))[0])
         return torch.stack(tembs).to(dt).contiguous()
 
+    def set_known(self, known, mask):
+        """Another picture to keep and / or another region (the next pose of a job): copied INTO the buffers the captured blend reads, no
+        re-capture.  known [bs or 1, 4, H, W], mask [1, 1, H, W] or as many rows as the sampler was built with."""
+        if not self.masked:
+            raise ValueError("this sampler was built without known / mask: its step and its graphs hold no blend")
+        if self.known_buf is None:  # before the first step
+            check_known(self.bs, known, mask)
+            self._known = (known, mask)
+            return
+        check_known(self.bs, known, mask, tuple(self.known_buf.shape))
+        if mask.shape[0] not in (1, self.mask_buf.shape[0]):
+            raise ValueError(f"a mask of {mask.shape[0]} rows for a sampler built with {self.mask_buf.shape[0]}")
+        self.known_buf.copy_(known)
+        self.mask_buf.copy_(mask)
+
+    def _blend(self, out, sigma_next):
+        """The end of a masked step, stated once for every solver and route: `out` = the latent after the solver's whole step, sigma_next
+        the step table (staged: the kernel reads column 1 of the step's row) or the schedule's own sigma_next as a device scalar."""
+        if not self.masked:
+            return out
+        from cd360 import ops
+        return ops.mask_blend(out, self.known_buf, self.mask_buf, sigma_next, self.gi, self.seed_buf, self.streams_buf)
+
     def _need_noise(self):
-        if not self._solver.draws(self):
+        if not (self.masked or self._solver.draws(self)):
             raise ValueError(f"solver {self.solver!r} with s_churn = {self.s_churn} draws no noise")
 
     def reseed(self, seed):
@@ -223,7 +300,7 @@ class Sampler:
     def _math_staged(self):
         """One sampler step on the static buffers, in place on self.gx, as the solver lays it out: for the one-evaluation solvers stage-in
         on step_tab / temb_tab -> UNet trunk -> the solver's tail kernel (for Euler the fused [c_out, CFG, to_d, Euler])."""
-        return self._solver.staged_step(self, self._evaluate)
+        return self._blend(self._solver.staged_step(self, self._evaluate), self.step_tab)
 
     def _unet(self, x_in, c_noise):
         return self.net(x_in, timesteps=c_noise, context=self.ctx, y=self.y, pose=self.pose)[0]
@@ -231,7 +308,7 @@ class Sampler:
     def _math(self, x, s, s_next):
         """One un-staged sampler step = guider.prepare_inputs -> DiscreteDenoiser (sigma -> table index, c_in) -> UNet -> the solver's
         fused tail kernel (for Euler [c_out, CFG, to_d, Euler]) on the row _set_step wrote."""
-        return self._solver.step(self, self._unet, x, s, s_next)
+        return self._blend(self._solver.step(self, self._unet, x, s, s_next), s_next)
 
     def _math_static(self):
         """The step as both graphs capture it: on the sampler's own buffers."""
@@ -355,15 +432,21 @@ class Sampler:
             self.gi.copy_(self._iota[i:i + 1])
             return
         self._solver.set_row(self, i)
+        if self.masked and solvers.GI not in self._solver.rows_of(self):  # (the blend's step word, where the solver itself reads none)
+            self.gi.copy_(self._iota[i:i + 1])
         if self.use_graph:
             self.gs[0].copy_(self.sigmas[i])
             self.gs[1].copy_(self.sigmas[i + 1])
 
     @torch.no_grad()
-    def step(self, x, i, alias: bool = False):
+    def step(self, x, i, alias: bool = False, first: bool = False):
         """Step i of the schedule on latent x.  alias=True (the job loop): the result may be the sampler's own latent buffer, valid until
-        the next call, and passing it straight back skips the copy-in -- a staged replay is then ONE 4-byte index copy plus the graph."""
+        the next call, and passing it straight back skips the copy-in -- a staged replay is then ONE 4-byte index copy plus the graph.
+        first=True: row i is the first step of an image (a trajectory that begins at `start_from`'s latent): the cached render is cleared
+        and the render runs there as it does on row 0 -- the render graph where row i has the captured shape, un-captured otherwise."""
         i = i % self.n_steps
+        if first:
+            check_first_step(self.solver, i, self.n_steps)
         # (eager launches of a staged sampler run the SAME staged step: the stage-in kernel's input convolution rounds a few outputs to the
         # other bf16 neighbour than the implicit-GEMM kernel does, and 70 random-init blocks amplify that to 1e-2 of eps -- graph and eager
         # must not differ by it; tests/test_f_rows_gpu.py holds the staged ends against the module arithmetic op by op)
@@ -379,13 +462,14 @@ class Sampler:
             self.gx.copy_(x)
         self._set_step(i)
         self.last_row = last = self._solver.single_row(self, i)
+        render = i == 0 or first
         if not self.use_graph:
-            if i == 0:
+            if render:
                 from cd360 import sampling
                 sampling.clear_rendered_feat(self.net)  # new image: the render runs again
                 self._state_layout()
             out = self._math_staged() if self.staged else self._math(x, self.sigmas[i], self.sigmas[i + 1])
-        elif i > 0:
+        elif not render:
             (self.lgraph if last else self.graph).replay()
             out = self.lout if last else self.gout
         elif self.rgraph is not None and not last:
@@ -404,33 +488,65 @@ def ops_kv8_buffers(k, heads):
             torch.empty(k.shape[0], heads, 2, dtype=torch.float32, device=k.device))
 
 
-def sample_assigned(sampler, jobs: Sequence[tuple], steps: int) -> List[torch.Tensor]:
+def sample_assigned(sampler, jobs: Sequence[tuple], steps: int, first_step: int = 0, edits=None) -> List[torch.Tensor]:
     """The per-rank loop of the job: `jobs` = [(pose, ctx, y, x0), ...] for the poses of this rank, in `shard.assign_poses` order; every
-    pose walks `steps` steps of the sampler's schedule from its own start latent (step 0 renders).  `sampler` needs `retarget(pose, ctx, y)`
-    and `step(x, i)` -- `Sampler` above; the gloo tests drive the same loop with a CPU stand-in."""
+    pose walks rows `first_step` .. `steps` - 1 of the sampler's schedule from its own start latent (the first of them renders).  `sampler`
+    needs `retarget(pose, ctx, y)` and `step(x, i)` -- `Sampler` above; the gloo tests drive the same loop with a CPU stand-in.
+    `edits`: one (known, mask) per job, handed to `sampler.set_known` before the pose's first step (masked sampling)."""
+    if first_step:
+        check_first_step(getattr(sampler, "solver", None), first_step, steps)
     finals = []
     for j, (pose, ctx, y, x0) in enumerate(jobs):
         if j > 0:
             sampler.retarget(pose, ctx, y)
+        if edits is not None:
+            sampler.set_known(*edits[j])
         x = x0.clone()
         alias = isinstance(sampler, Sampler)  # (the CPU stand-ins of the gloo tests take (x, i) only)
-        for i in range(steps):
-            x = sampler.step(x, i, alias=True) if alias else sampler.step(x, i)
+        for i in range(first_step, steps):
+            x = sampler.step(x, i, alias=True, first=i == first_step) if alias else sampler.step(x, i)
         finals.append(x.clone() if alias else x)
     return finals
 
 
-def sample_poses(make_sampler: Callable, make_job: Callable[[int], tuple], num_poses: int, steps: int, world: int = 1, rank: int = 0):
+def sample_poses(make_sampler: Callable, make_job: Callable[[int], tuple], num_poses: int, steps: int, world: int = 1, rank: int = 0,
+                 first_step: int = 0):
     """BASELINE configs[2] as a function: `num_poses` target poses over `world` ranks.  `make_job(p)` builds pose p's (pose, ctx, y, x0);
     `make_sampler(pose, ctx, y)` the rank's sampler for its first pose.  Returns (latents of ALL poses [num_poses, 4, L, L] in pose
-    order, identical on every rank; this rank's pose indices).  No collective on the data path; one all-gather at the end."""
+    order, identical on every rank; this rank's pose indices).  No collective on the data path; one all-gather at the end.
+    `first_step`: every pose walks rows first_step .. steps - 1 from its x0 (`start_from` makes one from a known latent)."""
     if num_poses < world:  # decided from the arguments alone, so EVERY rank raises (a rank-local check would leave the others in the all-gather)
         raise ValueError("more ranks than target poses: every rank needs at least one pose (the all-gather is sized per rank)")
     mine = shard.assign_poses(num_poses, world, rank)
     jobs = [make_job(p) for p in mine]
     sampler = make_sampler(*jobs[0][:3])
-    finals = sample_assigned(sampler, jobs, steps)
+    finals = sample_assigned(sampler, jobs, steps, first_step)
     return shard.gather_latents(torch.cat(finals, 0), num_poses), mine
+
+
+@torch.no_grad()
+def start_from(sampler, known: torch.Tensor, k: int, seed: int, streams=None) -> torch.Tensor:
+    """The latent a trajectory begins with at row k >= 1 of the sampler's schedule when it starts from a known latent instead of pure
+    noise (image-to-image): known + sigma_k z, [bs, 4, H, W] fp32, z = counter domain 3 at step word k - 1 under `seed` and the rows'
+    stream ids (default: stream 0 everywhere).  Computed by the blend itself with the mask 0 everywhere on row k - 1, so it is exactly the
+    latent a fully-kept masked run holds after step k - 1.  k = 0 is `start_latent`.  Reads `sampler.sigmas` / `sampler.bs` alone."""
+    from cd360 import ops
+    from cd360.sampler import seed_words
+    sig = sampler.sigmas
+    n = sig.numel() - 1
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k < n:
+        raise ValueError(f"k = {k!r}: start_from serves rows 1 .. {n - 1} of the {n}-step schedule (row 0 starts from noise alone: start_latent)")
+    bs = int(getattr(sampler, "bs", 1))
+    if streams is not None and len(streams) != bs:
+        raise ValueError(f"{len(streams)} noise stream ids for {bs} replay rows")
+    check_known(bs, known, torch.zeros((1, 1) + tuple(known.shape[2:])) if isinstance(known, torch.Tensor) and known.ndim == 4 else None)
+    dev = sig.device
+    known = known.to(dev).expand((bs,) + tuple(known.shape[1:])).contiguous()
+    seed_t = torch.tensor([seed_words(seed)], dtype=torch.int64, device=dev)
+    streams_t = None if streams is None else torch.tensor([int(v) for v in streams], dtype=torch.int32, device=dev)
+    step_t = torch.tensor([k - 1], dtype=torch.int32, device=dev)
+    keep = torch.zeros((1, 1) + tuple(known.shape[2:]), dtype=torch.float32, device=dev)
+    return ops.mask_blend(torch.zeros_like(known), known, keep, sig[k:k + 1].float().contiguous(), step_t, seed_t, streams_t)
 
 
 @torch.no_grad()
@@ -453,22 +569,39 @@ def start_latent(sampler, H: int, W: int, seed: int, streams=None) -> torch.Tens
 
 
 def sample_images(make_sampler: Callable, make_job: Callable[[int], tuple], num_poses: int, steps: int, first_stage, world: int = 1, rank: int = 0,
-                  seed: int = 0, latent_hw=None):
+                  seed: int = 0, latent_hw=None, first_step: int = 0, init_latents=None, masks=None):
     """Poses and a seed in, images out: `sample_poses` with the first stage on every rank.  `make_job(p)` builds pose p's (pose, ctx, y, x0);
     where x0 is None the pose starts from `start_latent(sampler, *latent_hw, seed)` -- stream 0, so all poses share their start noise as in
     sample.py:290-292 -- and `latent_hw` = (H, W) of the latent must be given.  Each rank decodes ITS poses with `first_stage.decode_u8`
     (cd360/images.py::FirstStage, or anything with that method); the one collective is an all-gather of the uint8 images.  Returns (images
-    [num_poses, H, W, 3] uint8 in pose order, identical on every rank and for every `world`; this rank's pose indices)."""
+    [num_poses, H, W, 3] uint8 in pose order, identical on every rank and for every `world`; this rank's pose indices).
+    `init_latents` [num_poses or 1, 4, H, W] (FirstStage.encode's output) with `masks` [num_poses or 1, 1, H, W] (images.latent_mask):
+    masked sampling -- `make_sampler` must build its Sampler with a known / mask of that shape, and every pose's own pair is handed to it
+    with `set_known`.  `first_step` > 0: every pose walks rows first_step .. steps - 1 only, and where x0 is None it starts from
+    `start_from(sampler, its init latent, first_step, seed)` (image-to-image; `init_latents` alone is enough for that)."""
     if num_poses < world:  # decided from the arguments alone, so EVERY rank raises (see sample_poses)
         raise ValueError("more ranks than target poses: every rank needs at least one pose (the all-gather is sized per rank)")
+    if masks is not None and init_latents is None:
+        raise ValueError("`masks` without `init_latents`: a region to keep needs the latent it keeps")
+    for name, t in (("init_latents", init_latents), ("masks", masks)):
+        if t is not None and (t.ndim != 4 or t.shape[0] not in (1, num_poses)):
+            raise ValueError(f"{name}: [{num_poses} or 1, ...] is needed, got {tuple(t.shape)}")
     mine = shard.assign_poses(num_poses, world, rank)
     jobs = [make_job(p) for p in mine]
     sampler = make_sampler(*jobs[0][:3])
+    of_pose = lambda t, p: t[p:p + 1] if t.shape[0] > 1 else t  # noqa: E731
+    if first_step:
+        check_first_step(getattr(sampler, "solver", None), first_step, steps)
+        if init_latents is None and any(j[3] is None for j in jobs):
+            raise ValueError("first_step > 0 with x0 = None: sample_images needs `init_latents` to start from")
+        jobs = [(pose, ctx, y, start_from(sampler, of_pose(init_latents, p), first_step, seed) if x is None else x)
+                for p, (pose, ctx, y, x) in zip(mine, jobs)]
     if any(j[3] is None for j in jobs):
         if latent_hw is None:
             raise ValueError("make_job returned x0 = None: sample_images needs latent_hw = (H, W) to draw the start latent")
         x0 = start_latent(sampler, int(latent_hw[0]), int(latent_hw[1]), seed)
         jobs = [(pose, ctx, y, x0 if x is None else x) for pose, ctx, y, x in jobs]
-    finals = sample_assigned(sampler, jobs, steps)
+    edits = None if masks is None else [(of_pose(init_latents, p), of_pose(masks, p)) for p in mine]
+    finals = sample_assigned(sampler, jobs, steps, first_step, edits)
     images = torch.cat([first_stage.decode_u8(x) for x in finals], 0)
     return shard.gather_latents(images, num_poses), mine

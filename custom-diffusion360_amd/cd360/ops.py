@@ -1795,6 +1795,58 @@ def vae_conv_out_u8(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torc
     return out
 
 
+# ----------------------------------------------------------------------------------------------- masked sampling (include/edit/cd360_edit.h)
+# libcd360_edit.so through cd360/_edit.py.  Refusals as above: ValueError before the device check and before the library is loaded.
+def _step_arg(step: torch.Tensor) -> None:
+    _refuse(not isinstance(step, torch.Tensor) or step.dtype != torch.int32 or step.numel() != 1,
+            f"step: a 1-element int32 tensor is needed, got {getattr(step, 'dtype', type(step))}")
+
+
+def edit_noise(seed: torch.Tensor, streams: Optional[torch.Tensor], step: torch.Tensor, bs: int, H: int, W: int) -> torch.Tensor:
+    """Standard normals [bs, 4, H, W] fp32 of counter domain 3 (cd360_edit_noise_f32, include/edit/cd360_edit.h): the noise mask_blend adds
+    to the known latent, a pure function of (seed, streams[row], step, channel, pixel) unrelated to sampler_noise / start_noise under the
+    same seed.  seed: device int64[1], step: device int32[1], streams: device int32[bs] or None (stream 0 for every row)."""
+    from . import _edit
+    _refuse(bs <= 0 or H <= 0 or W <= 0, f"bs, H, W must be positive, got {bs}, {H}, {W}")
+    _seed_args(seed, streams, bs)
+    _step_arg(step)
+    _need_gpu(seed, streams, step)
+    out = torch.empty((bs, 4, H, W), dtype=torch.float32, device=seed.device)
+    check(_edit.load().cd360_edit_noise_f32(_ptr(out), _ptr(seed), _ptr(streams), _ptr(step), bs, H * W, _stream()), "cd360_edit_noise_f32")
+    return out
+
+
+def mask_blend(x: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, sigma_next: torch.Tensor, step: torch.Tensor, seed: torch.Tensor,
+               streams: Optional[torch.Tensor]) -> torch.Tensor:
+    """The end of a masked sampling step, IN PLACE on x [bs, 4, H, W] fp32 (cd360_mask_blend_f32): x <- m x + (1 - m) kn with
+    kn = known + z s' (known itself where s' == 0), z = edit_noise(seed, streams, step, ...) drawn inside the kernel.  known [bs, 4, H, W]
+    fp32; mask [bs or 1, 1, H, W] fp32, 1 = generate, 0 = keep.  sigma_next: a step table [nsteps, 4] fp32 (s' = its column 1 in row
+    `step`: the staged step) or a 1-element fp32 tensor (s' itself: the un-staged step).  step: device int32[1]."""
+    from . import _edit
+    _refuse(not isinstance(x, torch.Tensor) or x.ndim != 4 or x.shape[1] != 4, f"x: [bs, 4, H, W] is needed, got {tuple(getattr(x, 'shape', ()))}")
+    bs, _, H, W = x.shape
+    _refuse(bs <= 0 or H * W <= 0, f"x is empty: {tuple(x.shape)}")
+    _f32_tensor(x, x.shape, "x")
+    _f32_tensor(known, x.shape, "known")
+    _refuse(not isinstance(mask, torch.Tensor) or mask.ndim != 4 or mask.shape[0] not in (1, bs),
+            f"mask: [{bs} or 1, 1, {H}, {W}] is needed, got {tuple(getattr(mask, 'shape', ()))}")
+    _f32_tensor(mask, (mask.shape[0], 1, H, W), "mask")
+    _refuse(not isinstance(sigma_next, torch.Tensor) or sigma_next.dtype != torch.float32 or not sigma_next.is_contiguous()
+            or not (sigma_next.numel() == 1 or (sigma_next.ndim == 2 and sigma_next.shape[1] == 4)),
+            "sigma_next: a contiguous fp32 step table [nsteps, 4] or a 1-element fp32 tensor is needed")
+    _seed_args(seed, streams, bs)
+    _step_arg(step)
+    _refuse(len({t.device for t in (x, known, mask, sigma_next, step, seed)} | ({streams.device} if streams is not None else set())) != 1,
+            "x, known, mask, sigma_next, step, seed and streams must be on one device")
+    _refuse(_overlaps(x, known) or _overlaps(x, mask), "x overlaps known or mask")
+    _need_gpu(x, known, mask, sigma_next, step, seed, streams)
+    table = sigma_next.numel() != 1
+    ptr = sigma_next.data_ptr() + (4 if table else 0)  # column 1 of the table's rows
+    check(_edit.load().cd360_mask_blend_f32(_ptr(x), _ptr(known), _ptr(mask), mask.shape[0], ptr, 4 if table else 0, _ptr(step), _ptr(seed),
+                                           _ptr(streams), bs, H * W, _stream()), "cd360_mask_blend_f32")
+    return x
+
+
 # ----------------------------------------------------------------------------------------------- rank-r adapters (add_lora=True)
 LOWRANK_RANKS = (8, 16, 32, 64)
 _DROPOUT_STATE = {}  # device -> int64 [2] (seed, offset) read by the mask of cd360_lowrank_add_bf16 / cd360_dropout_apply_bf16

@@ -305,11 +305,20 @@ class EulerEDMSampler(BaseDiffusionSampler):
         return min(self.s_churn / n_steps, 2 ** 0.5 - 1) if self.s_tmin <= sigma <= self.s_tmax else 0.0
 
     def __call__(self, denoiser: Callable, x, cond: Dict, uc=None, num_steps=None, mask=None, init_im=None):
+        """`mask` [N or 1, 1, H, W] at latent resolution (1 = generate, 0 = keep) with `init_im` [N, 4, H, W], the known latent as
+        encode_first_stage returns it: after every step the region to keep is replaced by init_im at the step's new noise level
+        (masked_blend).  The reference takes both arguments and never reads them (sampling.py:112-136).  That noise is torch.randn_like
+        for seed=None and, for seed=<int>, ops.edit_noise at the step's index: what cd360.job.Sampler(known=, mask=) draws inside its
+        captured step.  mask=None: today's arithmetic and draw order."""
+        check_edit_args(x, init_im, mask)
         x, s_in, sigmas, num_sigmas, cond, uc = self.prepare_sampling_loop(x, cond, uc, num_steps)
         rgb_list = None
         for i in range(num_sigmas - 1):
             gamma = self.gamma_of(sigmas[i], num_sigmas - 1)
             x, rgb_list = self.sampler_step(s_in * sigmas[i], s_in * sigmas[i + 1], denoiser, x, cond, uc, gamma)
+            if mask is not None:
+                noise = torch.randn_like(x) if self.seed is None else seeded_edit_noise(self, x, i)
+                x = masked_blend(x, init_im, mask, s_in * sigmas[i + 1], noise)
         return x, rgb_list
 
     forward = __call__
@@ -579,6 +588,51 @@ def seeded_noise(sampler, x: torch.Tensor, step: int) -> torch.Tensor:
                                      torch.zeros(1, dtype=torch.int32, device=x.device))
     sampler._noise.step.fill_(step)
     return sampler._noise.draw(x)
+
+
+# ----------------------------------------------------------------------------------------------- masked sampling (include/edit/cd360_edit.h)
+def masked_blend(x: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, sigma_next: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
+    """The end of a masked sampling step, in plain torch (CPU and GPU): the region to keep (mask 0) is replaced by the known latent at the
+    step's new noise level,
+
+        kn = known + noise * sigma_next   where sigma_next > 0, else known
+        x' = mask * x + (1 - mask) * kn
+
+    one fp32 rounding per operation, in the order cd360_mask_blend_f32 takes them.  x, known, noise [N, 4, H, W]; mask [N or 1, 1, H, W],
+    1 = generate; sigma_next [N], [1] or 0-d."""
+    s = append_dims(sigma_next.reshape(-1), x.ndim)
+    kn = torch.where(s > 0.0, known + noise * s, known)
+    return mask * x + (1.0 - mask) * kn
+
+
+def check_edit_args(x_shape, known, mask) -> None:
+    """What every sampler asks of (known latent, mask): both or neither; known shaped like the latent [N, 4, H, W], mask [N or 1, 1, H, W],
+    both fp32.  `x_shape`: the latent or its shape."""
+    shape = tuple(getattr(x_shape, "shape", x_shape))
+    if (known is None) != (mask is None):
+        raise ValueError("a mask needs the known latent it keeps (init_im / known) and the reverse: give both or neither")
+    if known is None:
+        return
+    if tuple(known.shape) != shape or known.dtype != torch.float32:
+        raise ValueError(f"the known latent must be fp32 of the latent's shape {shape}, got {known.dtype} {tuple(known.shape)}")
+    if mask.ndim != 4 or tuple(mask.shape) not in ((shape[0], 1) + shape[2:], (1, 1) + shape[2:]) or mask.dtype != torch.float32:
+        raise ValueError(f"the mask must be fp32 [{shape[0]} or 1, 1, {shape[2]}, {shape[3]}] at latent resolution (1 = generate), got "
+                         f"{mask.dtype} {tuple(mask.shape)}")
+
+
+def seeded_edit_noise(sampler, x: torch.Tensor, step: int) -> torch.Tensor:
+    """The seed=<int> noise of a masked step of the sampler classes: ops.edit_noise (counter domain 3) under `sampler.seed`, stream 0 and the
+    step's index; the buffers are kept on `sampler._edit_noise` per device.  GPU tensors only, as seeded_noise."""
+    from . import ops
+    if not x.is_cuda:
+        from ._lib import Cd360Error
+        raise Cd360Error(f"the seeded noise of {type(sampler).__name__} is drawn by a HIP kernel; got a CPU tensor (seed=None draws torch.randn_like)")
+    held = getattr(sampler, "_edit_noise", None)
+    if held is None or held[0].device != x.device:
+        held = sampler._edit_noise = (torch.tensor([seed_words(sampler.seed)], dtype=torch.int64, device=x.device),
+                                      torch.zeros(1, dtype=torch.int32, device=x.device))
+    held[1].fill_(step)
+    return ops.edit_noise(held[0], None, held[1], x.shape[0], x.shape[2], x.shape[3])
 
 
 class EulerAncestralSampler(BaseDiffusionSampler):

@@ -14,6 +14,7 @@
 constexpr uint32_t CD360_NOISE_STEP = 0u;       // inside a sampling step (include/cd360_stochastic.h, cd360_edm.h, cd360_highorder.h)
 constexpr uint32_t CD360_NOISE_START = 1u;      // the start of a trajectory (cd360_start_noise_f32)
 constexpr uint32_t CD360_NOISE_POSTERIOR = 2u;  // DiagonalGaussianDistribution.sample (cd360_posterior_sample_f32)
+constexpr uint32_t CD360_NOISE_EDIT = 3u;       // the known region of a masked step (csrc_edit/mask_blend.hip, include/edit/cd360_edit.h)
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t r[4]) {
 #pragma unroll
