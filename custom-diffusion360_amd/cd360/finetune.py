@@ -22,6 +22,7 @@ validation epoch on ~2 GB of bf16 features at 1024^2, as ONE collective per bloc
 from __future__ import annotations
 
 import collections
+import contextlib
 from typing import Dict, List, Optional
 
 import torch
@@ -204,10 +205,29 @@ class MasterAdamW:
     optimiser state and the accumulated weights live in fp32 and the bf16 parameters are refreshed from them after every step.
     bf16 parameters on the GPU take the fused path: masters and both moments in three flat fp32 buffers, the whole update (gradient
     read, decay, moments, bias-corrected step, bf16 write-back) in one pass of cd360_adamw_bf16 with the step count on the device
-    (graph-capturable as it is).  Anything else (CPU, fp32 parameters, amsgrad / maximize) runs torch.optim.AdamW on the masters."""
+    (graph-capturable as it is).  Anything else (CPU, fp32 parameters, amsgrad / maximize) runs torch.optim.AdamW on the masters.
 
-    def __init__(self, params, lr: float = 1e-5, fused: Optional[bool] = None, **kw):
+    max_grad_norm / ema_decay / live (all None: the object above, launch for launch).  Any of them set selects, on the fused path, the
+    LIVE step of include/optim/cd360_optim.h: lr and weight decay are read by the kernel from a device table that `sync_hyper()` refreshes
+    from `param_groups` (so a schedule reaches the replays of a captured step), `max_grad_norm` clips the global L2 norm of the gradients
+    as torch.nn.utils.clip_grad_norm_ does (one read-only pass for the norm, the factor applied inside the update; `grad_norm` and
+    `clip_coef` are 0-d device views, never read on the host), and `ema_decay` keeps LitEma's moving average (sgm/modules/ema.py,
+    use_num_upates=True) of the weights inside the same pass.  The shadows are fp32 where LitEma keeps the parameter dtype, for the reason
+    the masters exist: one EMA update moves a weight by (1 - decay) * delta ~ 1e-4 * delta, far below bf16's spacing, so a bf16 shadow
+    would never move.  `ema_scope()` swaps the averaged weights in, `ema_state_dict()` returns them.  Tensors without a gradient in a step
+    are skipped by that step, their shadows included.  The torch fall-back honours max_grad_norm (clip_grad_norm_ on the fp32 master
+    gradients) and ema_decay (the same formula in torch) too."""
+
+    def __init__(self, params, lr: float = 1e-5, fused: Optional[bool] = None, max_grad_norm: Optional[float] = None,
+                 ema_decay: Optional[float] = None, live: Optional[bool] = None, **kw):
         """`params`: an iterable of parameters, or optimiser groups as returned by optimizer_param_groups (per-group `lr`)."""
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"max_grad_norm must be >= 0, got {max_grad_norm}")
+        if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
+            raise ValueError("Decay must be between 0 and 1")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.live, self.ema, self._ema = False, None, None
         params = list(params)
         if params and isinstance(params[0], dict):
             groups = [{**{k: v for k, v in g.items() if k not in ("params", "names")}, "params": [p for p in g["params"] if p.requires_grad]}
@@ -239,6 +259,8 @@ class MasterAdamW:
                                  for g in groups]  # edit lr / weight_decay here (a captured graph keeps the values it was captured with)
             self._begin, self._plan, self._plan_key, self.opt, self.capturable = begin, None, None, None, True
             self._ops = ops
+            if self.max_grad_norm is not None or self.ema_decay is not None or live:
+                self._init_live(dev, begin, total)
             return
         self.master = [p.detach().float().clone() for p in self.params]
         it = iter(self.master)
@@ -246,6 +268,80 @@ class MasterAdamW:
         self.opt = torch.optim.AdamW([{**g, "params": [next(it) for _ in g["params"]]} for g in groups], lr=lr, **kw)
         self.param_groups = self.opt.param_groups
         self.capturable = all(g.get("capturable") for g in self.opt.param_groups)
+        if self.ema_decay is not None:
+            self.ema = [m.clone() for m in self.master]  # LitEma.__init__ clones the parameters
+            self._ema_updates = torch.zeros((), dtype=torch.float32, device=self.master[0].device) if self.master else None
+        if self.max_grad_norm is not None:
+            self.grad_norm = self.clip_coef = None  # set by step()
+
+    def _init_live(self, dev, begin, total) -> None:
+        """State of the live step: the (lr, weight decay) table, one row per tensor, in pinned host memory and on the device; the partial
+        sums and the 4 values (sumsq, norm, coef, 0) of the clip kernels; the flat fp32 EMA, initialised from the masters."""
+        self.live = True
+        n = len(self.params)
+        self._hyper_host = torch.zeros(n, 2, dtype=torch.float32).pin_memory()
+        self._hyper_dev = torch.zeros(n, 2, dtype=torch.float32, device=dev)
+        self._hyper_vals, self._hyper_event = None, None
+        chunks = (n + self._ops.ADAMW_MAX_TENSORS - 1) // self._ops.ADAMW_MAX_TENSORS
+        self._partials = torch.zeros(self._ops.sumsq_partials([total]) + chunks, dtype=torch.float32, device=dev)  # enough for any subset of the tensors
+        self._clip_out = torch.zeros(4, dtype=torch.float32, device=dev)
+        self.grad_norm, self.clip_coef = self._clip_out[1], self._clip_out[2]  # written by step() when max_grad_norm is set
+        if self.ema_decay is not None:
+            self._ema = self._master.clone()
+            self.ema = [self._ema[b:b + p.numel()].view(p.shape) for b, p in zip(begin, self.params)]
+        self.sync_hyper()
+
+    def sync_hyper(self) -> bool:
+        """The live step reads lr and weight decay from a device table: compare `param_groups` with the table's host copy and, on a change,
+        rewrite it and queue ONE non-blocking copy on the current stream.  Called by the eager step() and by GraphedTrainStep before every
+        replay; never captured.  Returns whether a copy was queued (always False for an optimiser that is not live)."""
+        if not self.live:
+            return False
+        vals = [(float(g["lr"]), float(g["weight_decay"])) for g in self.param_groups for _ in range(g["n"])]
+        if vals == self._hyper_vals:
+            return False
+        if self._hyper_event is not None:
+            self._hyper_event.synchronize()  # the previous copy has read the pinned rows before they are rewritten
+        self._hyper_host.copy_(torch.tensor(vals, dtype=torch.float32).view(-1, 2))
+        self._hyper_dev.copy_(self._hyper_host, non_blocking=True)
+        self._hyper_event = torch.cuda.Event()
+        self._hyper_event.record()
+        self._hyper_vals = vals
+        return True
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """The engine's ema_scope (sgm/models/diffusion.py:291-303): inside, the parameters hold the averaged weights (rounded to the
+        parameter dtype); on exit they hold the masters again.  Every weight cache keyed on `_version` is invalidated both times."""
+        if self.ema is None:
+            raise ValueError("ema_scope: this optimiser was built without ema_decay")
+        with torch.no_grad():
+            for p, e in zip(self.params, self.ema):
+                p.copy_(e)
+            self.bump_versions()
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                for p, m in zip(self.params, self.master):
+                    p.copy_(m)
+                self.bump_versions()
+
+    def ema_state_dict(self, names) -> Dict[str, torch.Tensor]:
+        """{name: fp32 shadow} for a checkpoint; `names` in the order of the optimiser's parameters."""
+        names = list(names)
+        if self.ema is None:
+            raise ValueError("ema_state_dict: this optimiser was built without ema_decay")
+        if len(names) != len(self.ema):
+            raise ValueError(f"ema_state_dict: {len(names)} names for {len(self.ema)} tensors")
+        return {k: e.detach().clone() for k, e in zip(names, self.ema)}
+
+    def _live_plan(self, active):
+        key = tuple(active)
+        if self._plan_key != key:
+            self._plan = self._ops.LiveAdamwPlan([self.params[i] for i in active], [self._begin[i] for i in active], list(active))
+            self._plan_key = key
+        return self._plan
 
     def bump_versions(self, active=None) -> None:
         """The fused kernel (and a hipGraph replay of it) writes the bf16 parameters through raw pointers, which torch's version counter
@@ -295,7 +391,17 @@ class MasterAdamW:
         if self.fused:
             # parameters without a gradient are skipped as torch does; the step count is one per optimiser, not one per tensor
             active = [i for i, p in enumerate(self.params) if p.grad is not None]
-            if active:
+            if active and self.live:
+                if not torch.cuda.is_current_stream_capturing():
+                    self.sync_hyper()
+                grads = [self.params[i].grad if self.params[i].grad.is_contiguous() else self.params[i].grad.contiguous() for i in active]
+                plan, coef = self._live_plan(active), None
+                if self.max_grad_norm is not None:
+                    coef = self._ops.grad_clip_coef(plan, grads, self._partials, self.max_grad_norm, self._clip_out)[2]
+                self._ops.adamw_live_step(plan, grads, self._hyper_dev, self._master, self.exp_avg, self.exp_avg_sq, self.steps, self.betas[0],
+                                          self.betas[1], self.eps, coef=coef, ema=self._ema, ema_decay=self.ema_decay or 0.0)
+                self.bump_versions(active)
+            elif active:
                 grads = [self.params[i].grad if self.params[i].grad.is_contiguous() else self.params[i].grad.contiguous() for i in active]
                 self._ops.adamw_step(self._fused_plan(active), grads, self._master, self.exp_avg, self.exp_avg_sq, self.steps, self.betas[0],
                                      self.betas[1], self.eps)
@@ -303,9 +409,44 @@ class MasterAdamW:
             return
         for m, p in zip(self.master, self.params):
             m.grad = None if p.grad is None else p.grad.float()
+        if self.max_grad_norm is not None:
+            with_grad = [m for m in self.master if m.grad is not None]
+            if with_grad:
+                self.grad_norm = torch.nn.utils.clip_grad_norm_(with_grad, self.max_grad_norm)
+                self.clip_coef = torch.clamp(self.max_grad_norm / (self.grad_norm + 1e-6), max=1.0)
         self.opt.step()
+        if self.ema is not None and any(m.grad is not None for m in self.master):
+            t = self._ema_updates.add_(1.0)  # LitEma.forward with use_num_upates=True, one fp32 operation at a time
+            omd = 1.0 - torch.clamp((1.0 + t) / (10.0 + t), max=self.ema_decay)
+            for e, m in zip(self.ema, self.master):
+                if m.grad is not None:
+                    e.sub_(omd * (e - m))
         for m, p in zip(self.master, self.params):
             p.copy_(m)
+
+
+class LRSchedule:
+    """torch.optim.lr_scheduler.LambdaLR's rule, lr = initial_lr * schedule(n), on the `param_groups` of a MasterAdamW (which LambdaLR
+    rejects: the class is not a torch Optimizer): applied at construction with n = 0 and at every step().  `schedule`: a callable of the
+    step number, e.g. one of sgm/lr_scheduler.py (DiffusionEngine.configure_optimizers, sgm/models/diffusion.py:362-374)."""
+
+    def __init__(self, optimizer, schedule):
+        self.optimizer, self.schedule, self.n = optimizer, schedule, 0
+        for g in optimizer.param_groups:
+            g.setdefault("initial_lr", g["lr"])
+        self.base_lrs = [g["initial_lr"] for g in optimizer.param_groups]
+        self._apply()
+
+    def _apply(self) -> None:
+        for g, base in zip(self.optimizer.param_groups, self.base_lrs):
+            g["lr"] = base * self.schedule(self.n)
+
+    def step(self) -> None:
+        self.n += 1
+        self._apply()
+
+    def get_last_lr(self) -> List[float]:
+        return [g["lr"] for g in self.optimizer.param_groups]
 
 
 _ADAPTERS = {}  # id(unet) -> (module epoch, whether any attention module carries add_lora adapters)
@@ -353,8 +494,10 @@ class GraphedTrainStep:
     Side effects of construction, all deliberate: (1) `warmup` REAL optimisation steps run on the construction batch before the capture
     (weights, moments and the device step counter advance by `warmup`; pass warmup_restore=True to snapshot and restore parameters,
     masters, moments and the step counter around them); (2) `device_rng = True` stays set on every raymarcher, so later eager steps draw
-    their patch jitter from the device generator too; (3) lr and weight_decay are frozen into the graph at capture time -- an LR scheduler
-    that edits `optimizer.param_groups` has no effect on replays (re-capture to change them)."""
+    their patch jitter from the device generator too; (3) unless the optimiser is LIVE (MasterAdamW(max_grad_norm= / ema_decay= / live=True)),
+    lr and weight_decay are frozen into the graph at capture time -- an LR scheduler that edits `optimizer.param_groups` then has no effect
+    on replays (re-capture to change them).  A live optimiser reads both from a device table that __call__ refreshes (sync_hyper, outside
+    the graph) before every replay: schedules reach the replays."""
 
     def __init__(self, unet: torch.nn.Module, loss_fn, optimizer: "MasterAdamW", batch: dict, warmup: int = 3, warmup_restore: bool = False,
                  weight_prefetch: bool = False, **loss_kw):
@@ -372,7 +515,7 @@ class GraphedTrainStep:
             saved = None
             if warmup_restore and optimizer.fused:
                 saved = ([p.detach().clone() for p in optimizer.params], optimizer._master.clone(), optimizer.exp_avg.clone(),
-                         optimizer.exp_avg_sq.clone(), optimizer.steps.clone())
+                         optimizer.exp_avg_sq.clone(), optimizer.steps.clone(), None if optimizer._ema is None else optimizer._ema.clone())
             for _ in range(warmup):
                 train_step(unet, loss_fn, optimizer, as_tensors=True, **self.static, **loss_kw)
             if saved is not None:
@@ -380,6 +523,8 @@ class GraphedTrainStep:
                     for p, q in zip(optimizer.params, saved[0]):
                         p.copy_(q)
                     optimizer._master.copy_(saved[1]); optimizer.exp_avg.copy_(saved[2]); optimizer.exp_avg_sq.copy_(saved[3]); optimizer.steps.copy_(saved[4])
+                    if saved[5] is not None:
+                        optimizer._ema.copy_(saved[5])
         torch.cuda.current_stream().wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         from . import memo
@@ -410,6 +555,8 @@ class GraphedTrainStep:
         """Copies `batch` (same keys and shapes as at construction; omitted keys keep their values) into the static buffers, replays."""
         for k, v in batch.items():
             self._load(self.static[k], v)
+        if hasattr(self.optimizer, "sync_hyper"):
+            self.optimizer.sync_hyper()  # a live optimiser: this step's lr / weight decay into the table the captured kernels read
         self.graph.replay()
         self.optimizer.bump_versions()  # the replay rewrote the parameters behind torch's back: invalidate every cache keyed on their version
         return self.total, self.logged

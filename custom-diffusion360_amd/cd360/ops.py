@@ -1044,6 +1044,93 @@ def adamw_step(plan: AdamwPlan, grads, master: torch.Tensor, exp_avg: torch.Tens
                                        _ptr(exp_avg_sq), _ptr(step), beta1, beta2, eps, _stream()), "cd360_adamw_bf16")
 
 
+# ----------------------------------------------------------------------------------------------- live optimiser step (include/optim/cd360_optim.h)
+# libcd360_optim.so through cd360/_optim.py: AdamwPlan / adamw_step above stay what they were.
+OPTIM_SUMSQ_VECS = 2048  # CD360_OPTIM_SUMSQ_VECS of include/optim/cd360_optim.h: 8-value vectors per workgroup, one partial each
+OPTIM_SUMSQ_TERMS = 64  # CD360_OPTIM_SUMSQ_TERMS: squares one thread adds before the workgroup's tree
+OPTIM_SUMSQ_DEPTH = 6  # CD360_OPTIM_SUMSQ_DEPTH: additions a square passes through inside its thread (a balanced tree)
+
+
+def sumsq_partials(numels) -> int:
+    """Partials one cd360_grad_sumsq_bf16 launch over tensors of these sizes writes (the header's formula)."""
+    return (sum((int(n) + 7) // 8 for n in numels) + OPTIM_SUMSQ_VECS - 1) // OPTIM_SUMSQ_VECS
+
+
+class LiveAdamwPlan:
+    """Host-side argument arrays of cd360_grad_sumsq_bf16 / cd360_adamw_live_bf16 for a fixed list of bf16 parameters: what AdamwPlan holds,
+    with each tensor's row of the device (lr, weight decay) table in place of the values, and each chunk's slice of the partial sums
+    (`part0`, `parts`; `npartials` in all).  Gradient and parameter pointers are refreshed on every step, as there."""
+
+    def __init__(self, params, begin, rows):
+        self.n = len(params)
+        self.params = list(params)
+        assert all(p.dtype == torch.bfloat16 and p.is_contiguous() for p in self.params)
+        self.chunks, self.npartials = [], 0
+        for c0 in range(0, self.n, ADAMW_MAX_TENSORS):
+            idx = list(range(c0, min(self.n, c0 + ADAMW_MAX_TENSORS)))
+            k = len(idx)
+            parts = sumsq_partials(params[i].numel() for i in idx)
+            self.chunks.append(dict(
+                idx=idx, k=k, grads=(ctypes.c_void_p * k)(), params=(ctypes.c_void_p * k)(*[params[i].data_ptr() for i in idx]),
+                begin=(ctypes.c_int64 * k)(*[int(begin[i]) for i in idx]), numel=(ctypes.c_int64 * k)(*[params[i].numel() for i in idx]),
+                row=(ctypes.c_int32 * k)(*[int(rows[i]) for i in idx]), part0=self.npartials, parts=parts))
+            self.npartials += parts
+
+    def refresh(self, grads) -> None:
+        assert len(grads) == self.n and all(g.dtype == torch.bfloat16 and g.is_contiguous() for g in grads)
+        for c in self.chunks:
+            for j, i in enumerate(c["idx"]):
+                c["grads"][j] = grads[i].data_ptr()
+                c["params"][j] = self.params[i].data_ptr()
+                assert grads[i].numel() == c["numel"][j] == self.params[i].numel()
+
+
+def grad_clip_coef(plan: LiveAdamwPlan, grads, partials: torch.Tensor, max_norm: float, out: torch.Tensor) -> torch.Tensor:
+    """out[4] fp32 <- (sumsq, norm, coef, 0) of the bf16 gradients `grads` (plan order, contiguous): cd360_grad_sumsq_bf16 per chunk into
+    its slice of `partials` (fp32, at least plan.npartials entries; every entry read is written first), then cd360_grad_clip_f32 with
+    coef = min(1, max_norm / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s rule.  No host read; bit-reproducible."""
+    from . import _optim
+    _refuse(not (float(max_norm) >= 0.0), f"max_norm must be >= 0, got {max_norm}")
+    _refuse(partials.dtype != torch.float32 or not partials.is_contiguous() or partials.numel() < plan.npartials,
+            f"partials: contiguous fp32 with at least {plan.npartials} entries is needed")
+    _refuse(out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != 4 or out.data_ptr() % 16 != 0, "out: 4 contiguous fp32 values, 16-byte aligned")
+    _refuse(_overlaps(out, partials), "out overlaps partials")
+    _need_gpu(partials, out, *grads)
+    lib = _optim.load()
+    plan.refresh(grads)
+    with _timed("grad_sumsq", 0.0, 2.0 * sum(g.numel() for g in grads)):
+        for c in plan.chunks:
+            check(lib.cd360_grad_sumsq_bf16(c["k"], c["grads"], c["numel"], partials.data_ptr() + 4 * c["part0"], _stream()), "cd360_grad_sumsq_bf16")
+    check(lib.cd360_grad_clip_f32(_ptr(partials), plan.npartials, float(max_norm), _ptr(out), _stream()), "cd360_grad_clip_f32")
+    return out
+
+
+def adamw_live_step(plan: LiveAdamwPlan, grads, hyper: torch.Tensor, master: torch.Tensor, exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
+                    step: torch.Tensor, beta1: float, beta2: float, eps: float, coef: Optional[torch.Tensor] = None,
+                    ema: Optional[torch.Tensor] = None, ema_decay: float = 0.0) -> None:
+    """One AdamW step of every tensor of `plan` (cd360_adamw_tick + cd360_adamw_live_bf16): adamw_step with lr / weight decay read on the
+    device from `hyper` [rows, 2] fp32, the gradient scaled by the device scalar `coef` (None: as it is) and `ema` (flat fp32 like
+    `master`; None: none) moved towards the new master with decay min(ema_decay, (1 + t) / (10 + t)), t = the step count after the tick."""
+    from . import _optim
+    flat = (master, exp_avg, exp_avg_sq) + (() if ema is None else (ema,))
+    _refuse(any(t.dtype != torch.float32 or not t.is_contiguous() for t in flat + (step, hyper) + (() if coef is None else (coef,))),
+            "master, exp_avg, exp_avg_sq, ema, step, hyper and coef must be contiguous fp32 tensors")
+    _refuse(hyper.ndim != 2 or hyper.shape[1] != 2 or hyper.shape[0] < 1, f"hyper: [rows, 2] is needed, got {tuple(hyper.shape)}")
+    _refuse(any(t.numel() != master.numel() for t in flat), "master, exp_avg, exp_avg_sq and ema must have one length")
+    _refuse(coef is not None and coef.numel() != 1, "coef: one fp32 value")
+    _refuse(ema is not None and any(_overlaps(ema, t) for t in (master, exp_avg, exp_avg_sq)), "ema overlaps master or a moment")
+    _need_gpu(*flat, step, hyper, coef, *grads)
+    first, lib = _lib.load(), _optim.load()
+    plan.refresh(grads)
+    check(first.cd360_adamw_tick(_ptr(step), _stream()), "cd360_adamw_tick")
+    total = sum(g.numel() for g in grads)
+    with _timed("adamw_live", 0.0, (28.0 if ema is None else 36.0) * total):
+        for c in plan.chunks:
+            check(lib.cd360_adamw_live_bf16(c["k"], c["grads"], c["params"], c["begin"], c["numel"], c["row"], _ptr(hyper), hyper.shape[0], _ptr(coef),
+                                            _ptr(master), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(ema), float(ema_decay), _ptr(step), beta1, beta2,
+                                            eps, _stream()), "cd360_adamw_live_bf16")
+
+
 def gemm_tn_ok(a: torch.Tensor, b: torch.Tensor) -> bool:
     if not (a.is_cuda and a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and a.stride(-1) == 1 and b.stride(-1) == 1):
         return False
