@@ -198,6 +198,32 @@ def load_delta_state_dict(unet: torch.nn.Module, sd_delta: Dict[str, object], pr
     return list(unexpected)
 
 
+def load_delta_embeddings(conditioner: torch.nn.Module, embed) -> None:
+    """sgm/util.py:216-230 for the conditioner part: `embed` = sd_delta["embed"], the trained modifier rows of the two prompt encoders
+    (embed[0] for conditioner.embedders[0], FrozenCLIPEmbedder; embed[1] for embedders[1], FrozenOpenCLIPEmbedder; each [k, D]).  The
+    reference sets every token table to torch.cat([checkpoint table without modifier rows, embed[i]]).  Here the embedder already holds
+    its k modifier rows (appended at construction): the LAST k rows of its table are overwritten; a table that holds none yet (an embedder
+    built without modifier_token) gets them appended.  `embed` and its tensors are not modified."""
+    for emb, rows in zip(conditioner.embedders[:2], embed):
+        table = emb._tables()[0]
+        rows = rows.detach().to(table.device, table.dtype)
+        if rows.dim() != 2 or rows.shape[1] != table.shape[1]:
+            raise ValueError(f"delta embedding rows {tuple(rows.shape)} for a token table of width {table.shape[1]}")
+        k = rows.shape[0]
+        held = len(getattr(emb, "modifier_token_id", None) or ())
+        if held not in (0, k):
+            raise ValueError(f"{type(emb).__name__} holds {held} modifier rows, the delta checkpoint {k}")
+        with torch.no_grad():
+            if held:
+                table[table.shape[0] - k:].copy_(rows)  # in place: the version counter moves and cd360.derived rebuilds what was packed
+            else:
+                holder = emb.transformer.text_model.embeddings.token_embedding if hasattr(emb, "transformer") else emb.model.token_embedding
+                V = table.shape[0]
+                holder.weight = torch.nn.Parameter(torch.cat([table.detach(), rows], 0), requires_grad=table.requires_grad)
+                holder.num_embeddings = V + k
+                emb.modifier_token_id = list(range(V, V + k))
+
+
 # ---------------------------------------------------------------- one optimisation step
 class MasterAdamW:
     """AdamW (configs/train_co3d_concept.yaml: optimizer_config AdamW) on fp32 master copies of the trainable parameters: the HIP

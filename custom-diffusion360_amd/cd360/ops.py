@@ -2048,3 +2048,84 @@ def lora_ok(x: torch.Tensor, base_out: torch.Tensor, down: torch.Tensor, up: tor
         return False
     M = x.numel() // max(K, 1)
     return gemm_ok(M, r, K) and gemm_ok(M, r, N) and N % 16 == 0 and base_out.stride(-1) == 1
+
+
+# ----------------------------------------------------------------------------------------------- prompt encoders (include/text/cd360_text.h)
+# libcd360_text.so through cd360/_text.py.  Forward only: a tensor on a tape raises (_need_gpu).
+TEXT_MAX_TOKENS = 128  # CD360_TEXT_MAX_TOKENS
+ACT_QUICK_GELU, ACT_GELU = 0, 1
+
+
+def text_embed(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, want_stats: bool = False, ids_host: Optional[torch.Tensor] = None):
+    """bf16(fp32(tok[ids]) + fp32(pos[n])) -> [B, N, D] bf16 (cd360_text_embed_bf16); want_stats=True returns (out, stats fp32 [B*N, 1, 2]),
+    the row statistics gemm(..., ln=...) reads.  ids int64 [B, N] on the GPU; tok [V, D], pos [>= N, D] bf16 contiguous.  `ids_host`: the same
+    ids where they came from (a CPU tensor): checked against [0, V) here, before the launch -- the kernel itself writes a zero row for an id
+    outside the table and reads nothing out of bounds."""
+    _need_gpu(ids, tok, pos)
+    assert ids.dtype == torch.int64 and ids.dim() == 2 and ids.is_contiguous()
+    assert tok.dtype == torch.bfloat16 and pos.dtype == torch.bfloat16 and tok.dim() == 2 and pos.dim() == 2 and tok.is_contiguous() and pos.is_contiguous()
+    B, N = ids.shape
+    V, D = tok.shape
+    assert pos.shape[0] >= N and pos.shape[1] == D
+    if ids_host is not None and ids_host.numel() and (int(ids_host.min()) < 0 or int(ids_host.max()) >= V):
+        raise ValueError(f"token ids outside the table: [{int(ids_host.min())}, {int(ids_host.max())}] for {V} rows")
+    out = torch.empty(B, N, D, dtype=torch.bfloat16, device=ids.device)
+    stats = torch.empty(B * N, 1, 2, dtype=torch.float32, device=ids.device) if want_stats else None
+    from . import _text
+    with _timed("text_embed", 0.0, 2.0 * 3 * B * N * D):
+        check(_text.load().cd360_text_embed_bf16(_ptr(ids), _ptr(tok), _ptr(pos), _ptr(out), B, N, V, D, D, _ptr(stats), _stream()),
+              "cd360_text_embed_bf16")
+    return (out, stats) if want_stats else out
+
+
+def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, scale: float = 64 ** -0.5, n: Optional[int] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Causal softmax(scale q k^T) v per head, head dim 64, at most TEXT_MAX_TOKENS tokens (cd360_text_causal_attn_bf16).  q, k, v
+    [b, >= n, H*64] with a contiguous last dim and free row / batch strides (the three column slices of one merged q|k|v projection are
+    consumed in place) -> [b, n, H*64].  `n` limits the tokens when the buffers hold more rows: rows >= n are never read."""
+    _need_gpu(q, k, v)
+    b, rows, inner = q.shape
+    n = rows if n is None else n
+    assert inner == heads * 64 and q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16 and v.dtype == torch.bfloat16
+    assert q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1 and k.shape[-1] == inner and v.shape[-1] == inner
+    assert 1 <= n <= TEXT_MAX_TOKENS and rows >= n and k.shape[1] >= n and v.shape[1] >= n and k.shape[0] == b and v.shape[0] == b
+    if out is None:
+        out = torch.empty(b, n, inner, dtype=torch.bfloat16, device=q.device)
+    assert out.shape == (b, n, inner) and out.dtype == torch.bfloat16 and out.stride(2) == 1
+    strides = (_I64x3(q.stride(0), 64, q.stride(1)), _I64x3(k.stride(0), 64, k.stride(1)),
+               _I64x3(v.stride(0), 64, v.stride(1)), _I64x3(out.stride(0), 64, out.stride(1)))
+    from . import _text
+    with _timed("text_causal_attn", 2.0 * b * heads * n * (n + 1) * 64, 2.0 * 4 * b * n * inner):
+        check(_text.load().cd360_text_causal_attn_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(out), b, heads, n, *strides, float(scale), _stream()),
+              "cd360_text_causal_attn_bf16")
+    return out
+
+
+def text_activation(x: torch.Tensor, kind: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """kind ACT_QUICK_GELU: x * sigmoid(1.702 x); ACT_GELU: exact (erf) GELU -- fp32 inside, bf16 in and out (cd360_text_act_bf16).
+    x [..., n] bf16 whose leading dims collapse to uniformly strided rows; out like x (default: a fresh contiguous tensor; out=x: in place)."""
+    _need_gpu(x)
+    rows, ld = _rows2d(x)
+    n = x.shape[-1]
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    ro, ldo = _rows2d(out)
+    assert ro == rows and out.shape[-1] == n
+    from . import _text
+    with _timed("text_act", 0.0, 2.0 * 2 * rows * n):
+        check(_text.load().cd360_text_act_bf16(_ptr(x), _ptr(out), rows, n, ld, ldo, int(kind), _stream()), "cd360_text_act_bf16")
+    return out
+
+
+def eot_pool(x: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """x [B, N, D] bf16, ids int64 [B, N] on the GPU -> [B, D]: row argmax_n ids[b, n] of every prompt, the lowest index on ties; the argmax
+    runs on the device (cd360_text_eot_pool_bf16)."""
+    _need_gpu(x, ids)
+    assert x.dtype == torch.bfloat16 and x.dim() == 3 and x.stride(2) == 1 and x.stride(0) == x.shape[1] * x.stride(1)
+    assert ids.dtype == torch.int64 and ids.is_contiguous() and tuple(ids.shape) == tuple(x.shape[:2])
+    B, N, D = x.shape
+    out = torch.empty(B, D, dtype=torch.bfloat16, device=x.device)
+    from . import _text
+    with _timed("text_eot_pool", 0.0, 2.0 * 2 * B * D):
+        check(_text.load().cd360_text_eot_pool_bf16(_ptr(x), _ptr(ids), _ptr(out), B, N, D, x.stride(1), D, _stream()), "cd360_text_eot_pool_bf16")
+    return out
