@@ -183,32 +183,40 @@ class Cd360Error(RuntimeError):
     pass
 
 
-def load(check_symbols: bool = True):
-    """dlopen the library and type every entry point.  Raises if anything is missing."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
+def bind(path, table, check_symbols: bool = True):
+    """dlopen the library at `path` and type every entry point of `table` (name -> (restype, argtypes)): the one loader of every cd360
+    library.  Raises if the file is missing, and for a symbol it does not export unless check_symbols=False, which leaves that symbol
+    unbound.  Reads no environment variable and keeps nothing: caching is the caller's."""
+    if not os.path.exists(path):
         raise Cd360Error(
-            f"{LIB_PATH} not found: the HIP extension has not been built (run `python __graft_entry__.py`). "
+            f"{path} not found: the HIP extension has not been built (run `python __graft_entry__.py`). "
             "There is no CPU or PyTorch fallback for the cd360 operators."
         )
-    # torch FIRST: its wheel carries its own HIP runtime (torch/lib/libamdhip64.so), and the device pointers and streams this library
+    # torch FIRST: its wheel carries its own HIP runtime (torch/lib/libamdhip64.so), and the device pointers and streams a library
     # is handed belong to THAT runtime.  Loaded before torch, libcd360_hip.so would pull in the system runtime (/opt/rocm/lib) as a second
     # copy in the process and every launch on torch's streams would fail ("HIP launch failure": build() followed by smoke() in one
-    # process did exactly that).  With torch's runtime already mapped, the dynamic loader binds this library's libamdhip64 dependency to it.
+    # process did exactly that).  With torch's runtime already mapped, the dynamic loader binds the library's libamdhip64 dependency to it.
     import torch  # noqa: F401
-    lib = ctypes.CDLL(LIB_PATH)
-    if os.environ.get("CD360_LIB"):
-        check_symbols = False  # an explicitly named older / probe build (same-box A/B): entry points it predates stay unbound
-    for name, (res, args) in ((name, sig) for table in ABI.values() for name, sig in table.items()):
+    lib = ctypes.CDLL(path)
+    for name, (res, args) in table.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
             if check_symbols:
-                raise Cd360Error(f"libcd360_hip.so does not export {name}") from e
+                raise Cd360Error(f"{os.path.basename(path)} does not export {name}") from e
             continue
         fn.restype, fn.argtypes = res, args
+    return lib
+
+
+def load(check_symbols: bool = True):
+    """bind() libcd360_hip.so to every table of ABI, once; then the one-time read of TUNING_ENV.  Raises if anything is missing."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if os.environ.get("CD360_LIB"):
+        check_symbols = False  # an explicitly named older / probe build (same-box A/B): entry points it predates stay unbound
+    lib = bind(LIB_PATH, {name: sig for table in ABI.values() for name, sig in table.items()}, check_symbols)
     _lib = lib
     env = {}
     for name, field in TUNING_ENV.items():

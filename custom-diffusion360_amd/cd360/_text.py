@@ -1,17 +1,15 @@
 """ctypes binding of libcd360_text.so (the C ABI declared in include/text/cd360_text.h): the prompt encoders' token + position embedding,
 causal self-attention, MLP activation and EOT pooling.
 
-A fourth library with a table of its own: the first library's headers, tables and exports are closed (cd360/_lib.py::ABI names exactly
-the headers of include/*.h) and so are the second's and the third's (cd360/_edit.py, cd360/_optim.py), so TEXT_SIGNATURES is entered in
-none of them.  There is NO fallback: if the shared library is missing or a symbol is absent this module raises.  The library is built
-in-tree by `__graft_entry__.build()` next to libcd360_hip.so.  No environment variable is read."""
+A library with a table of its own, entered in no older library's: DESIGN.md ("Why a second library") says why,
+tests/sampler_cases.py::check_library_matches_table holds every library to it.  Bound by cd360._lib.bind: no fallback, no environment
+variable."""
 from __future__ import annotations
 
-import ctypes
 import os
 from ctypes import POINTER, c_float, c_int, c_int64, c_void_p
 
-from ._lib import Cd360Error, check  # noqa: F401  (check: the error codes are those of include/cd360_hip.h)
+from ._lib import Cd360Error, bind, check  # noqa: F401  (check: the error codes are those of include/cd360_hip.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libcd360_text.so")
@@ -33,24 +31,8 @@ _lib = None
 
 
 def load():
-    """dlopen the library and type every entry point.  Raises if anything is missing."""
+    """The library, bound by cd360._lib.bind on the first call."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise Cd360Error(
-            f"{LIB_PATH} not found: the HIP extension has not been built (run `python __graft_entry__.py`). "
-            "There is no CPU or PyTorch fallback for the cd360 operators."
-        )
-    # torch FIRST, as in cd360._lib.load: the device pointers and streams this library is handed belong to the HIP runtime of torch's wheel,
-    # and with that runtime already mapped the dynamic loader binds this library's libamdhip64 dependency to it
-    import torch  # noqa: F401
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in TEXT_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise Cd360Error(f"libcd360_text.so does not export {name}") from e
-        fn.restype, fn.argtypes = res, args
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = bind(LIB_PATH, TEXT_SIGNATURES)
+    return _lib

@@ -227,6 +227,20 @@ def guarded(arena: Arena, modules=None, lib=None):
             L.load = saved_load
 
 
+@contextlib.contextmanager
+def recorded(guard, module):
+    """Inside guarded()'s context: record the entry points of `module`'s library as well (guarded() records cd360._lib.load()'s library;
+    cd360.ops reaches the others through cd360._edit.load(), cd360._optim.load(), cd360._text.load()), into the same list P4 reads."""
+    rec = Recorder(module.load())
+    saved = module.load
+    module.load = lambda: rec
+    try:
+        yield rec
+    finally:
+        module.load = saved
+        guard.lib.called.extend(rec.called)
+
+
 def _flatten(x, out=None, path="result"):
     out = [] if out is None else out
     if isinstance(x, torch.Tensor):

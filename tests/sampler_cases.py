@@ -77,6 +77,24 @@ def declared_functions(header):
     return set(re.findall(r"\b(?:int|int64_t)\s+(cd360_\w+)\s*\(", src))
 
 
+def header_constant(header, name):
+    m = re.search(r"#define\s+%s\s+(\d+)" % name, header_text(header))
+    assert m, name
+    return int(m.group(1))
+
+
+def _header_table_library(header, table, new_names, older_tables, older_headers, lib):
+    """The rule itself: -> (mismatch, in_older_tables, in_older_headers, mistyped, lib), the first four empty when it holds."""
+    new = set(new_names)
+    declared = set(re.findall(r"\b(cd360_[a-z0-9_]+)\s*\(", header_text(header)))
+    mismatch = (declared ^ set(table)) | (declared ^ new)
+    in_older_tables = {n for t in older_tables for n in t} & new
+    in_older_headers = [h for h in older_headers if any(n in header_text(h) for n in new)]
+    mistyped = [n for n in new_names if not (isinstance(getattr(lib, n), ctypes._CFuncPtr) and getattr(lib, n).restype is ctypes.c_int
+                                             and list(getattr(lib, n).argtypes) == table[n][1])]
+    return mismatch, in_older_tables, in_older_headers, mistyped, lib
+
+
 def check_header_matches_table(header, table, new_names, older_headers):
     """include/<header> <=> its signature table, by the rule test_library_exports_every_declared_symbol holds cd360_hip.h to (every
     `cd360_...(` word, comments included).  -> (mismatch, in_older_tables, in_older_headers, mistyped, lib): the names on which header,
@@ -84,15 +102,37 @@ def check_header_matches_table(header, table, new_names, older_headers):
     library does not export as typed; and the library itself (loaded with check_symbols=True).  The first four must be empty."""
     from cd360 import _lib
     assert _lib.ABI[header] is table and all(h in _lib.ABI for h in older_headers)
-    new = set(new_names)
-    declared = set(re.findall(r"\b(cd360_[a-z0-9_]+)\s*\(", header_text(header)))
-    mismatch = (declared ^ set(table)) | (declared ^ new)
-    in_older_tables = {n for h in older_headers for n in _lib.ABI[h]} & new
-    in_older_headers = [h for h in older_headers if any(n in header_text(h) for n in new)]
-    lib = _lib.load(check_symbols=True)
-    mistyped = [n for n in new_names if not (isinstance(getattr(lib, n), ctypes._CFuncPtr) and getattr(lib, n).restype is ctypes.c_int
-                                             and list(getattr(lib, n).argtypes) == table[n][1])]
-    return mismatch, in_older_tables, in_older_headers, mistyped, lib
+    return _header_table_library(header, table, new_names, [_lib.ABI[h] for h in older_headers], older_headers, _lib.load(check_symbols=True))
+
+
+# every library in the order it was added: (header folder under include/, binding module of cd360, its table there, the names its header
+# declares).  The first library's tables are cd360._lib.ABI, its headers include/*.h; a new library enters itself at the end.
+LIBRARIES = [
+    ("", "_lib", None, None),
+    ("edit", "_edit", "EDIT_SIGNATURES", ["cd360_edit_noise_f32", "cd360_mask_blend_f32"]),
+    ("optim", "_optim", "OPTIM_SIGNATURES", ["cd360_grad_sumsq_bf16", "cd360_grad_clip_f32", "cd360_adamw_live_bf16"]),
+    ("text", "_text", "TEXT_SIGNATURES", ["cd360_text_embed_bf16", "cd360_text_causal_attn_bf16", "cd360_text_act_bf16", "cd360_text_eot_pool_bf16"]),
+]
+
+
+def check_library_matches_table(position):
+    """LIBRARIES[position], a library beside the first: its header <=> its table <=> the loaded library, by the rule of
+    check_header_matches_table, and every older library closed to it.  -> (mismatch, in_tables, in_headers, mistyped, lib): the names on
+    which header, table and the entry's names disagree; the new names a table of cd360._lib.ABI or of an earlier entry holds; the headers
+    in the folders of the earlier entries (listed from include/, bound or not) that name one; the new names the library does not export as
+    typed; the library.  The first four must be empty."""
+    import importlib
+    from cd360 import _lib
+    assert 0 < position < len(LIBRARIES)
+    folder, module, attr, new_names = LIBRARIES[position]
+    mod = importlib.import_module("cd360." + module)
+    table = getattr(mod, attr)
+    assert mod.HEADER == os.path.join(folder, os.path.basename(mod.HEADER))
+    older_tables = list(_lib.ABI.values()) + [getattr(importlib.import_module("cd360." + m), a) for _, m, a, _ in LIBRARIES[1:position]]
+    assert all(t is not table for t in older_tables)
+    inc = os.path.join(ROOT, "include")
+    older_headers = [os.path.join(d, f) for d, _, _, _ in LIBRARIES[:position] for f in os.listdir(os.path.join(inc, d)) if f.endswith(".h")]
+    return _header_table_library(mod.HEADER, table, new_names, older_tables, older_headers, mod.load())
 
 
 def check_guarded_cover(header, table, guarded_cases):

@@ -23,7 +23,7 @@ def test_edit_header_matches_its_table_and_the_first_library_is_closed():
     name is in a table of cd360._lib.ABI, in a header of include/*.h or exported by libcd360_hip.so; _lib.ABI is the six headers it was,
     each table holding exactly its header's names; null pointers and a mask of 2 rows for 3 samples are refused on the host."""
     from cd360 import _edit, _lib
-    mismatch, in_tables, in_headers, mistyped, lib = EC.check_header_matches_table()
+    mismatch, in_tables, in_headers, mistyped, lib = SC.check_library_matches_table(EC.LIBRARY)
     assert not mismatch, mismatch
     assert not in_tables, in_tables
     assert not in_headers, in_headers

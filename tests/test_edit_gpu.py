@@ -106,7 +106,7 @@ def test_edit_entry_points_write_their_outputs_only(declares, mask_rows, row):
     """Both entry points under tests/guarded.py at HW = 35, bs = 3, both poison patterns: x, known and the mask live in arena blocks between
     canaries, so no guard byte changes; the results are finite and bit-equal between the poisons; the operands are unchanged; both entry
     points ran."""
-    from cd360 import ops
+    from cd360 import _edit, ops
     bs, H, Wd = 3, 5, 7
     inputs = dict(x=R(bs, 4, H, Wd, seed=4), known=R(bs, 4, H, Wd, seed=5), mask=torch.rand(mask_rows, 1, H, Wd, device=DEV), tab=_table(),
                   step=step_t(row), seed=seed_t(BIG_SEED), streams=streams_t([0, 3, 0]))
@@ -117,7 +117,7 @@ def test_edit_entry_points_write_their_outputs_only(declares, mask_rows, row):
         gx, gk, gm = (T.empty(tuple(t.shape), dtype=t.dtype, device=DEV) for t in (x, known, mask))
         for g, t in ((gx, x), (gk, known), (gm, mask)):
             g.copy_(t)
-        with EC.recorded(guard):
+        with G.recorded(guard, _edit):
             z = ops.edit_noise(seed, streams, step, bs, H, Wd)
             out = ops.mask_blend(gx, gk, gm, tab, step, seed, streams)
         assert out is gx and torch.equal(gk, known) and torch.equal(gm, mask)

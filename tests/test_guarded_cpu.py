@@ -200,6 +200,28 @@ def test_recorder_notes_calls_not_lookups():
     assert rec.called == ["cd360_fake_other"]
 
 
+def test_recorded_adds_a_second_library_to_the_guards_list_and_restores_load():
+    """guarded.recorded on a fake module: calls through module.load() land in the guard's list next to the first library's; module.load
+    is the module's own again after a normal exit and after the body raised, and returns the same library object as before."""
+    m, lib = fake_binding()
+    other, load = FakeLib(), m.load
+    with G.guarded(G.Arena(0xFF), modules=[m], lib=other) as g:
+        g.lib.cd360_fake_other()
+        with G.recorded(g, m) as rec:
+            assert m.load() is rec and m.load is not load
+            m.load().cd360_fake_other()
+            m.load().not_an_entry_point()
+            m.scale2(torch.ones(2, 3))
+        assert m.load is load and m.load() is lib
+        assert g.lib.called == ["cd360_fake_other", "cd360_fake_other", "cd360_fake_scale2"]
+        with pytest.raises(RuntimeError, match="boom"):
+            with G.recorded(g, m):
+                m.load().cd360_fake_other()
+                raise RuntimeError("boom")
+        assert m.load is load and m.load() is lib
+        assert g.lib.called[3:] == ["cd360_fake_other"] and g.called == {"cd360_fake_other", "cd360_fake_scale2"}
+
+
 # ---------------------------------------------------------------------------------------------------------------- arena / proxy
 @pytest.mark.parametrize("poison", G.POISONS)
 @pytest.mark.parametrize("shape, dtype", [((3, 5, 7), torch.bfloat16), ((1,), torch.float32), ((0,), torch.uint8), ((1000, 300), torch.float32),

@@ -274,6 +274,26 @@ def test_library_exports_every_declared_symbol():
     assert lib.cd360_conv_stats_slabs(320) == 4 and lib.cd360_conv_stats_slabs(640) == 2 and lib.cd360_conv_k_order(1280, 9) == 5
 
 
+def test_bind_is_the_one_loader_and_names_what_is_missing(tmp_path):
+    """cd360._lib.bind: a missing file and a symbol the library does not export raise with the texts every library's loader had;
+    check_symbols=False leaves the absent symbol unbound and types the rest; the module's own cached library is untouched."""
+    from cd360 import _edit, _lib
+    mine = _edit.load()
+    missing = str(tmp_path / "libcd360_absent.so")
+    with pytest.raises(_lib.Cd360Error) as e:
+        _lib.bind(missing, _edit.EDIT_SIGNATURES)
+    assert missing in str(e.value) and "__graft_entry__.py" in str(e.value) and "has not been built" in str(e.value)
+    table = {**_edit.EDIT_SIGNATURES, "cd360_no_such_entry": (ctypes.c_int, [])}
+    with pytest.raises(_lib.Cd360Error) as e:
+        _lib.bind(_edit.LIB_PATH, table)
+    assert str(e.value) == "libcd360_edit.so does not export cd360_no_such_entry"
+    lib = _lib.bind(_edit.LIB_PATH, table, check_symbols=False)
+    assert len(_edit.EDIT_SIGNATURES) == 2
+    for name, (res, args) in _edit.EDIT_SIGNATURES.items():
+        assert getattr(lib, name).restype is res and list(getattr(lib, name).argtypes) == args, name
+    assert _edit.load() is mine and _edit.load() is _edit._lib
+
+
 def test_every_header_is_bound_by_exactly_one_signature_table():
     """cd360._lib.ABI names every header under include/ and nothing else; the functions each header declares outside comments are the
     keys of its table, one for one; no name is typed twice.  A header added without a table, or a table load() never binds, fails here."""

@@ -26,7 +26,7 @@ def test_optim_header_matches_its_table_and_the_older_libraries_are_closed():
     new name is in a table of cd360._lib.ABI, in EDIT_SIGNATURES, in a header of the first two libraries or exported by either; the
     binding reads no environment variable; the constants of the header are those cd360.ops computes slice lengths with."""
     from cd360 import _edit, _lib, _optim, ops
-    mismatch, in_tables, in_headers, mistyped, lib = OC.check_header_matches_table()
+    mismatch, in_tables, in_headers, mistyped, lib = SC.check_library_matches_table(OC.LIBRARY)
     assert not mismatch, mismatch
     assert not in_tables, in_tables
     assert not in_headers, in_headers
@@ -37,9 +37,9 @@ def test_optim_header_matches_its_table_and_the_older_libraries_are_closed():
         assert not hasattr(first, name) and not hasattr(second, name), name
     src = open(_optim.__file__).read()
     assert "os.environ" not in src and "getenv" not in src
-    assert OC.header_constant("CD360_OPTIM_SUMSQ_VECS") == ops.OPTIM_SUMSQ_VECS and OC.header_constant("CD360_OPTIM_SUMSQ_TERMS") == ops.OPTIM_SUMSQ_TERMS
+    assert SC.header_constant(OC.HEADER, "CD360_OPTIM_SUMSQ_VECS") == ops.OPTIM_SUMSQ_VECS and SC.header_constant(OC.HEADER, "CD360_OPTIM_SUMSQ_TERMS") == ops.OPTIM_SUMSQ_TERMS
     assert ops.OPTIM_SUMSQ_VECS * 8 == 256 * ops.OPTIM_SUMSQ_TERMS  # 256 threads, each its share of the workgroup's vectors
-    assert OC.header_constant("CD360_OPTIM_SUMSQ_DEPTH") == ops.OPTIM_SUMSQ_DEPTH and 2 ** ops.OPTIM_SUMSQ_DEPTH == ops.OPTIM_SUMSQ_TERMS
+    assert SC.header_constant(OC.HEADER, "CD360_OPTIM_SUMSQ_DEPTH") == ops.OPTIM_SUMSQ_DEPTH and 2 ** ops.OPTIM_SUMSQ_DEPTH == ops.OPTIM_SUMSQ_TERMS
     assert ops.sumsq_partials([1]) == 1 and ops.sumsq_partials([8 * 2048]) == 1 and ops.sumsq_partials([8 * 2048 + 1]) == 2
     assert ops.sumsq_partials([8 * 2047, 1, 1]) == 2  # vectors, not values: every tensor's tail is a vector of its own
 

@@ -393,7 +393,7 @@ def test_optim_entry_points_write_their_outputs_only(declares):
     result values, masters, moments, EMA and the step count live in arena blocks between canaries (the padding between tensors of the flat
     buffers is poisoned too), so no guard byte changes; the results are finite and bit-equal between the poisons; gradients and hyper are
     unchanged by all three, the partials by the clip kernel; all three entry points ran."""
-    from cd360 import ops
+    from cd360 import _optim, ops
     g = torch.Generator(device=DEV).manual_seed(3)
     inputs = {}
     for i, s in enumerate(G_SHAPES):
@@ -430,7 +430,7 @@ def test_optim_entry_points_write_their_outputs_only(declares):
         for vm, ve, w in zip(views(master), views(ema), gw):
             vm.copy_(w)
             ve.copy_(w)
-        with OC.recorded(guard) as rec:
+        with G.recorded(guard, _optim) as rec:
             ops.grad_clip_coef(plan, gg, partials, 0.5, out)
             kept, first = partials.clone(), out.clone()
             assert rec.cd360_grad_clip_f32(partials.data_ptr(), plan.npartials, 0.5, out.data_ptr(), torch.cuda.current_stream().cuda_stream) == 0

@@ -19,7 +19,7 @@ def test_text_header_matches_its_table_and_the_older_libraries_are_closed():
     """include/text/cd360_text.h <=> cd360._text.TEXT_SIGNATURES <=> libcd360_text.so (every `cd360_...(` word, comments included); no new
     name is in a table or a header of the three older libraries or exported by them; the binding reads no environment variable."""
     from cd360 import _edit, _lib, _optim, _text
-    mismatch, in_tables, in_headers, mistyped, lib = TC.check_header_matches_table()
+    mismatch, in_tables, in_headers, mistyped, lib = SC.check_library_matches_table(TC.LIBRARY)
     assert not mismatch, mismatch
     assert not in_tables, in_tables
     assert not in_headers, in_headers
@@ -32,7 +32,7 @@ def test_text_header_matches_its_table_and_the_older_libraries_are_closed():
     hip = open(os.path.join(SC.ROOT, "custom-diffusion360_amd", "csrc_text", "text_encoder.hip")).read()
     assert "getenv" not in hip and "Synchronize" not in hip
     from cd360 import ops
-    assert TC.header_constant("CD360_TEXT_MAX_TOKENS") == ops.TEXT_MAX_TOKENS == _text.MAX_TOKENS == 128
+    assert SC.header_constant(TC.HEADER, "CD360_TEXT_MAX_TOKENS") == ops.TEXT_MAX_TOKENS == _text.MAX_TOKENS == 128
 
 
 def test_text_entry_points_refuse_bad_arguments_on_the_host():

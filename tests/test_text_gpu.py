@@ -376,14 +376,14 @@ def test_conditioner_on_the_hip_route_and_into_the_sampler():
 
 # ================================================================================================ 8: guarded memory
 def _guarded_case(case):
-    from cd360 import ops
+    from cd360 import _text, ops
     g = torch.Generator().manual_seed(81)
     if case == "embed-stats":
         inputs = dict(ids=torch.randint(0, 96, (3, 77), generator=g).to(DEV), tok=_bf(96, 128, seed=82), pos=_bf(77, 128, seed=83))
 
         @SC.guardfn
         def fn(guard, ids, tok, pos):
-            with TC.recorded(guard):
+            with G.recorded(guard, _text):
                 out, stats = ops.text_embed(ids, tok, pos, want_stats=True)
             return dict(out=out, stats=stats)
     elif case == "causal-attn-merged":
@@ -395,7 +395,7 @@ def _guarded_case(case):
             D = H * 64
             buf = guard.torch.empty((B, rows, 3 * D), dtype=BF, device=DEV)
             buf[:, :N].copy_(qkv)
-            with TC.recorded(guard):
+            with G.recorded(guard, _text):
                 out = ops.causal_attention(buf[..., :D], buf[..., D:2 * D], buf[..., 2 * D:], H, n=N)
             assert torch.equal(out, ops_attn_plain(qkv, H))
             return dict(out=out)
@@ -410,7 +410,7 @@ def _guarded_case(case):
         def fn(guard, x, big):
             wide = guard.torch.empty((5, 64), dtype=BF, device=DEV)  # the 16 columns behind every ragged row stay poison
             wide[:, :48].copy_(x)
-            with TC.recorded(guard):
+            with G.recorded(guard, _text):
                 outs = [ops.text_activation(wide[:, :48], kind) for kind in (0, 1)] + [ops.text_activation(big, kind) for kind in (0, 1)]
             return dict(outs=outs)
     else:
@@ -419,7 +419,7 @@ def _guarded_case(case):
 
         @SC.guardfn
         def fn(guard, x, ids):
-            with TC.recorded(guard):
+            with G.recorded(guard, _text):
                 return dict(out=ops.eot_pool(x, ids))
     return fn, inputs
 

@@ -1,18 +1,16 @@
 """What tests/test_text_cpu.py and tests/test_text_gpu.py share (plain helper module, like optim_cases.py; no tests, no fixtures): the names
-include/text/cd360_text.h adds, the header / table / library rule restated for the FOURTH library, a recorder for libcd360_text.so under
-tests/guarded.py, the small architectures, and builders of the embedders next to their tests/text_fp32.py reference on one state dict."""
-import contextlib
-import ctypes
+include/text/cd360_text.h adds (the library's entry in sampler_cases.LIBRARIES, where the header / table / library rule is stated), the
+small architectures, and builders of the embedders next to their tests/text_fp32.py reference on one state dict."""
 import json
 import os
-import re
 
 import torch
 
 import sampler_cases as SC
 import text_fp32 as T32
 
-NEW = ["cd360_text_embed_bf16", "cd360_text_causal_attn_bf16", "cd360_text_act_bf16", "cd360_text_eot_pool_bf16"]
+LIBRARY = 3  # in SC.LIBRARIES
+NEW = SC.LIBRARIES[LIBRARY][3]
 HEADER = os.path.join("text", "cd360_text.h")
 KERNELS = ("text_embed_kernel", "text_causal_attn_kernel", "text_act_kernel", "text_eot_pool_kernel")
 # the guarded cases of tests/test_text_gpu.py::test_text_entry_points_write_their_outputs_only: (id, entry points the case must reach)
@@ -23,49 +21,6 @@ SMALL = dict(vocab=96, width=128, heads=2, layers=3, mlp=512, proj=128)
 # the real widths, one layer each
 CLIP_L = dict(vocab=96, width=768, heads=12, layers=1, mlp=3072, proj=768)
 BIG_G = dict(vocab=96, width=1280, heads=20, layers=1, mlp=5120, proj=1280)
-
-
-def check_header_matches_table():
-    """include/text/cd360_text.h <=> cd360._text.TEXT_SIGNATURES <=> the loaded libcd360_text.so, by the rule of
-    sampler_cases.check_header_matches_table (every `cd360_...(` word of the header, comments included).  -> (mismatch, in_tables,
-    in_headers, mistyped, lib); the first four must be empty."""
-    from cd360 import _edit, _lib, _optim, _text
-    table = _text.TEXT_SIGNATURES
-    assert all(t is not table for t in _lib.ABI.values()) and _edit.EDIT_SIGNATURES is not table and _optim.OPTIM_SIGNATURES is not table
-    new = set(NEW)
-    declared = set(re.findall(r"\b(cd360_[a-z0-9_]+)\s*\(", SC.header_text(HEADER)))
-    mismatch = (declared ^ set(table)) | (declared ^ new)
-    in_tables = ({n for t in _lib.ABI.values() for n in t} | set(_edit.EDIT_SIGNATURES) | set(_optim.OPTIM_SIGNATURES)) & new
-    inc = os.path.join(SC.ROOT, "include")
-    older = [f for f in os.listdir(inc) if f.endswith(".h")]
-    older += [os.path.join(d, f) for d in ("edit", "optim") for f in os.listdir(os.path.join(inc, d)) if f.endswith(".h")]
-    in_headers = [h for h in older if any(n in SC.header_text(h) for n in new)]
-    lib = _text.load()
-    mistyped = [n for n in NEW if not (isinstance(getattr(lib, n), ctypes._CFuncPtr) and getattr(lib, n).restype is ctypes.c_int
-                                       and list(getattr(lib, n).argtypes) == table[n][1])]
-    return mismatch, in_tables, in_headers, mistyped, lib
-
-
-def header_constant(name):
-    m = re.search(r"#define\s+%s\s+(\d+)" % name, SC.header_text(HEADER))
-    assert m, name
-    return int(m.group(1))
-
-
-@contextlib.contextmanager
-def recorded(guard):
-    """Inside tests/guarded.py's context: record the entry points of libcd360_text.so as well (cd360.ops reaches the fourth library through
-    cd360._text.load()), into the same list P4 reads."""
-    import guarded as G
-    from cd360 import _text
-    rec = G.Recorder(_text.load())
-    saved = _text.load
-    _text.load = lambda: rec
-    try:
-        yield rec
-    finally:
-        _text.load = saved
-        guard.lib.called.extend(rec.called)
 
 
 # ------------------------------------------------------------------------------------------------ embedders and their references
