@@ -224,6 +224,54 @@ def load_delta_embeddings(conditioner: torch.nn.Module, embed) -> None:
                 emb.modifier_token_id = list(range(V, V + k))
 
 
+class TokenRows(torch.nn.Module):
+    """The trainable modifier-token rows of a conditioner's prompt encoders (train_tokens): `parameters()` are the rows, one [k, D] leaf per
+    marked embedder in the order of conditioner.embedders -- one more optimiser group for MasterAdamW (bf16 on the GPU: its fused path).
+    The embedders are held, not owned: they stay the conditioner's sub-modules."""
+
+    def __init__(self, embedders, rows):
+        super().__init__()
+        self.rows = torch.nn.ParameterList(rows)
+        self.__dict__["embedders"] = list(embedders)
+
+    def embeds(self) -> List[torch.Tensor]:
+        """Copies of the rows, the list delta_state_dict(embeds=) stores and load_delta_embeddings reads."""
+        return [r.detach().clone() for r in self.rows]
+
+    @torch.no_grad()
+    def sync(self) -> None:
+        """Write the rows into the last k rows of the embedders' token tables, in place (the version counter moves): for sampling under
+        no_grad after training.  A grad-enabled forward of a marked embedder does the same on its own."""
+        for emb, r in zip(self.embedders, self.rows):
+            table = emb._tables()[0]
+            table[table.shape[0] - r.shape[0]:].copy_(r)
+
+
+def train_tokens(conditioner: torch.nn.Module) -> TokenRows:
+    """Opt in to training the modifier-token embeddings (sgm/models/diffusion.py:342-355 hands both token tables to the optimiser;
+    modules.py:499-511, 724-730 lets the gradient through at the modifier positions only; the delta checkpoint keeps exactly those rows).
+    For each of conditioner.embedders[:2] with `modifier_token_id`: a leaf parameter [k, D] holding the last k rows of its token table, in the
+    table's dtype and on its device (call this AFTER moving the conditioner), requires_grad=True; the table itself is set to
+    requires_grad=False and the embedder is marked (`embedder.token_rows`, kept out of its parameters and its state dict).  A marked
+    embedder called with grad enabled runs cd360.grad.TextTowerFn on the HIP route, the masked embedding on the torch route.  An embedder
+    without modifier tokens is skipped; ValueError if none has any.  Unlike the reference, only these k rows are optimiser parameters (its
+    whole 49409-row tables are, their other rows receiving zero gradient and weight decay only, and the delta checkpoint drops them)."""
+    marked, rows = [], []
+    for emb in list(conditioner.embedders)[:2]:
+        k = len(getattr(emb, "modifier_token_id", None) or ())
+        if not k:
+            continue
+        table = emb._tables()[0]
+        r = torch.nn.Parameter(table.detach()[table.shape[0] - k:].clone().contiguous(), requires_grad=True)
+        table.requires_grad = False
+        emb.__dict__["token_rows"] = r
+        marked.append(emb)
+        rows.append(r)
+    if not rows:
+        raise ValueError("train_tokens: no prompt encoder of this conditioner has modifier tokens (modifier_token is None)")
+    return TokenRows(marked, rows)
+
+
 # ---------------------------------------------------------------- one optimisation step
 class MasterAdamW:
     """AdamW (configs/train_co3d_concept.yaml: optimizer_config AdamW) on fp32 master copies of the trainable parameters: the HIP

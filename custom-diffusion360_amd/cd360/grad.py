@@ -449,3 +449,70 @@ class LoraFn(torch.autograd.Function):
 
 def lora(x, base_out, down, up, p, site):
     return LoraFn.apply(x, base_out, down, up, p, site)
+
+
+def _text_layer_bwd(L, heads: int, kind: int, eps: float, x_in, qkv, x_mid, h, d_out):
+    """One layer of a prompt encoder, backward: d_out [B, N, D] at the layer's output -> the gradient at its input.  Eight launches; every
+    weight is frozen, so the Linears have a data gradient only (dX = dY W on cd360_gemm_bf16 with the transposed weight; FC1 and q|k|v with
+    the UNFOLDED weight: the LayerNorm's gain is applied inside add_layernorm_bwd, which also joins the residual's gradient)."""
+    from .derived import derived
+    D = x_in.shape[-1]
+    d_h = ops.gemm(d_out, ops.weight_t(L.fc2.weight))
+    ops.text_activation_bwd(h, d_h, kind, out=d_h)
+    d_ln2 = ops.gemm(d_h, ops.weight_t(L.fc1.weight))
+    d_mid = ops.add_layernorm_bwd(x_mid, L.ln2.weight.detach(), d_ln2, d_out, eps)
+    d_o = ops.gemm(d_mid, ops.weight_t(L.out.weight))
+    dqkv = torch.empty_like(qkv)
+    sl = lambda t: (t[..., :D], t[..., D:2 * D], t[..., 2 * D:])
+    ops.causal_attention_bwd(*sl(qkv), d_o, heads, out=sl(dqkv))
+    wt = derived(L.owner, "_cd360_qkv_t", tuple(L.qkv[0]), lambda: L.merged_qkv()[0].detach().t().contiguous())
+    d_ln1 = ops.gemm(dqkv, wt)
+    return ops.add_layernorm_bwd(x_in, L.ln1.weight.detach(), d_ln1, d_mid, eps)
+
+
+class TextTowerFn(torch.autograd.Function):
+    """One walk over a prompt encoder of sgm.modules.encoders.modules (FrozenCLIPEmbedder, FrozenOpenCLIPEmbedder) on the HIP route, for
+    an embedder that finetune.train_tokens marked.  The one differentiable input is `rows` [k, D], the modifier rows (already copied into
+    the last k rows of the token table); the reference lets the gradient through at the modifier positions only
+    ((1 - indices) * x.detach() + indices * x, modules.py:499-511, 724-730), which is exactly the gradient of those rows.
+    Forward: tower._hip_outputs -- the launches of the no-tape route, bit for bit, with the activation written out of place -- and per
+    layer the layer's input, the merged q|k|v projection, the stream behind the attention and the pre-activation are kept (the attention
+    output is not: no weight gradient reads it and the attention backward recomputes its probabilities).  `wants` names the results:
+    "pen", "last_ln", "pen_ln", "pooled".  Backward: pooled -> GEMM on text_projection as stored -> eot_scatter; the final LayerNorm; per
+    layer, last to first, _text_layer_bwd; the penultimate gradient joins at the input of the last layer; token_rows_grad."""
+
+    @staticmethod
+    def forward(ctx, rows, tower, ids, wants):
+        tape = []
+        outs = tower._hip_outputs(ids, wants, tape)
+        last = tape.pop()
+        ctx.save_for_backward(ids, last, *(t for entry in tape for t in entry))
+        ctx.tower, ctx.wants, ctx.k, ctx.dtype = tower, tuple(wants), rows.shape[0], rows.dtype
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        ids, last, *flat = ctx.saved_tensors
+        tower = ctx.tower
+        layers, eps = tower._layers(), float(tower._final_ln().eps)  # one eps for every LayerNorm of a tower
+        lnw = tower._final_ln().weight.detach()
+        g = {w: (None if d is None else d.to(torch.bfloat16).contiguous()) for w, d in zip(ctx.wants, grads)}
+        d_last_ln = g.get("last_ln")
+        if g.get("pooled") is not None:
+            d_row = ops.gemm(g["pooled"], tower.model.text_projection.detach())  # [B, P] x ([D, P] as stored)^T
+            d_last_ln = torch.zeros_like(last) if d_last_ln is None else d_last_ln.clone()  # autograd's buffer is not ours to write
+            ops.eot_scatter(d_row, ids, d_last_ln)
+        dx = None if d_last_ln is None else ops.add_layernorm_bwd(last, lnw, d_last_ln, None, eps)
+        d_pen = g.get("pen")
+        if g.get("pen_ln") is not None:
+            d_pen = ops.add_layernorm_bwd(flat[-4], lnw, g["pen_ln"], d_pen, eps)
+        for i in range(len(layers) - 1, -1, -1):
+            if dx is not None:
+                dx = _text_layer_bwd(layers[i], tower.heads, tower.act_kind, eps, *flat[4 * i:4 * i + 4], dx)
+            if i == len(layers) - 1 and d_pen is not None:
+                dx = d_pen if dx is None else dx + d_pen  # (one bf16 add of [B, N, D] per step, in torch)
+        if dx is None:
+            return torch.zeros(ctx.k, last.shape[-1], dtype=ctx.dtype, device=last.device), None, None, None
+        V = tower._tables()[0].shape[0]
+        return ops.token_rows_grad(dx, ids, range(V - ctx.k, V)).to(ctx.dtype), None, None, None

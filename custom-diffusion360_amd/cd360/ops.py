@@ -2129,3 +2129,90 @@ def eot_pool(x: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     with _timed("text_eot_pool", 0.0, 2.0 * 2 * B * D):
         check(_text.load().cd360_text_eot_pool_bf16(_ptr(x), _ptr(ids), _ptr(out), B, N, D, x.stride(1), D, _stream()), "cd360_text_eot_pool_bf16")
     return out
+
+
+# ----------------------------------------------------------------------------------------------- prompt encoders, backward (include/textgrad/cd360_textgrad.h)
+# libcd360_textgrad.so through cd360/_textgrad.py: what grad.TextTowerFn launches beside gemm() and add_layernorm_bwd().
+TEXTGRAD_MAX_MODIFIERS = 3  # CD360_TEXTGRAD_MAX_MODIFIERS
+
+
+def _head_strides(t: torch.Tensor):
+    return _I64x3(t.stride(0), 64, t.stride(1))
+
+
+def causal_attention_bwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, d_o: torch.Tensor, heads: int, scale: float = 64 ** -0.5,
+                         n: Optional[int] = None, out=None):
+    """Backward of causal_attention (cd360_textgrad_causal_attn_bwd_bf16): q, k, v as there (the three column slices of the saved merged
+    projection are consumed in place), d_o [b, >= n, H*64] -> (dq, dk, dv), the three column slices of ONE fresh [b, n, 3*H*64] buffer, or
+    the three tensors of `out`.  The probabilities are recomputed in fp32; no atomics: the same bits on every run.  Rows >= n are neither
+    read nor written."""
+    _need_gpu(q, k, v, d_o)
+    b, rows, inner = q.shape
+    n = rows if n is None else n
+    assert inner == heads * 64 and all(t.dtype == torch.bfloat16 and t.dim() == 3 and t.stride(2) == 1 and t.shape[2] == inner and t.shape[0] == b
+                                       and t.shape[1] >= n for t in (q, k, v, d_o))
+    assert 1 <= n <= TEXT_MAX_TOKENS
+    if out is None:
+        buf = torch.empty(b, n, 3 * inner, dtype=torch.bfloat16, device=q.device)
+        out = (buf[..., :inner], buf[..., inner:2 * inner], buf[..., 2 * inner:])
+    dq, dk, dv = out
+    assert all(t.dtype == torch.bfloat16 and t.dim() == 3 and t.stride(2) == 1 and t.shape[2] == inner and t.shape[0] == b and t.shape[1] >= n
+               for t in out)
+    from . import _textgrad
+    with _timed("textgrad_causal_attn_bwd", 5 * 2.0 * b * heads * n * (n + 1) / 2 * 64, 2.0 * 7 * b * n * inner):
+        check(_textgrad.load().cd360_textgrad_causal_attn_bwd_bf16(_ptr(q), _ptr(k), _ptr(v), _ptr(d_o), _ptr(dq), _ptr(dk), _ptr(dv), b, heads, n,
+                                                                   *(_head_strides(t) for t in (q, k, v, d_o, dq, dk, dv)), float(scale), _stream()),
+              "cd360_textgrad_causal_attn_bwd_bf16")
+    return dq, dk, dv
+
+
+def text_activation_bwd(x: torch.Tensor, dy: torch.Tensor, kind: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dy * f'(x) for the activation `kind` of text_activation, x the saved pre-activation (cd360_textgrad_act_bwd_bf16): fp32 inside, bf16 in
+    and out.  x, dy [..., n] bf16 whose leading dims collapse to uniformly strided rows; out like dy (default: fresh; out=dy: in place)."""
+    _need_gpu(x, dy)
+    rows, ld = _rows2d(x)
+    rd, ldd = _rows2d(dy)
+    n = x.shape[-1]
+    if out is None:
+        out = torch.empty(dy.shape, dtype=torch.bfloat16, device=dy.device)
+    ro, ldo = _rows2d(out)
+    assert rd == rows and ro == rows and dy.shape[-1] == n and out.shape[-1] == n
+    from . import _textgrad
+    with _timed("textgrad_act_bwd", 0.0, 2.0 * 3 * rows * n):
+        check(_textgrad.load().cd360_textgrad_act_bwd_bf16(_ptr(x), _ptr(dy), _ptr(out), rows, n, ld, ldd, ldo, int(kind), _stream()),
+              "cd360_textgrad_act_bwd_bf16")
+    return out
+
+
+def eot_scatter(d_pooled: torch.Tensor, ids: torch.Tensor, dx: torch.Tensor) -> torch.Tensor:
+    """Backward of eot_pool, IN PLACE on dx [B, N, D] bf16: row argmax_n ids[b, n] of prompt b (the lowest index on ties, found on the device)
+    becomes bf16(fp32(row) + fp32(d_pooled[b])); every other row stays (cd360_textgrad_eot_scatter_bf16).  -> dx."""
+    _need_gpu(d_pooled, ids, dx)
+    assert dx.dtype == torch.bfloat16 and dx.dim() == 3 and dx.stride(2) == 1 and dx.stride(0) == dx.shape[1] * dx.stride(1)
+    assert ids.dtype == torch.int64 and ids.is_contiguous() and tuple(ids.shape) == tuple(dx.shape[:2])
+    B, N, D = dx.shape
+    assert d_pooled.dtype == torch.bfloat16 and tuple(d_pooled.shape) == (B, D) and d_pooled.stride(1) == 1
+    from . import _textgrad
+    with _timed("textgrad_eot_scatter", 0.0, 2.0 * 3 * B * D):
+        check(_textgrad.load().cd360_textgrad_eot_scatter_bf16(_ptr(d_pooled), _ptr(ids), _ptr(dx), B, N, D, d_pooled.stride(0) if B > 1 else D,
+                                                               dx.stride(1), _stream()), "cd360_textgrad_eot_scatter_bf16")
+    return dx
+
+
+def token_rows_grad(d_x0: torch.Tensor, ids: torch.Tensor, modifier_ids) -> torch.Tensor:
+    """d_x0 [B, N, D] bf16 (the gradient at the embedding's output), ids int64 [B, N] on the GPU, modifier_ids: up to TEXTGRAD_MAX_MODIFIERS
+    host ints -> fp32 [k, D]: for every modifier id the sum of the rows of d_x0 at the positions that hold it, in rising (b, n) order; a zero
+    row for a modifier that occurs nowhere (cd360_textgrad_token_rows_f32).  No atomics: the same bits on every run."""
+    _need_gpu(d_x0, ids)
+    assert d_x0.dtype == torch.bfloat16 and d_x0.dim() == 3 and d_x0.stride(2) == 1 and d_x0.stride(0) == d_x0.shape[1] * d_x0.stride(1)
+    assert ids.dtype == torch.int64 and ids.is_contiguous() and tuple(ids.shape) == tuple(d_x0.shape[:2])
+    mods = [int(m) for m in modifier_ids]
+    k = len(mods)
+    assert 1 <= k <= TEXTGRAD_MAX_MODIFIERS
+    B, N, D = d_x0.shape
+    out = torch.empty(k, D, dtype=torch.float32, device=d_x0.device)
+    from . import _textgrad
+    with _timed("textgrad_token_rows", 0.0, 2.0 * B * N * D + 4.0 * k * D):
+        check(_textgrad.load().cd360_textgrad_token_rows_f32(_ptr(d_x0), _ptr(ids), (ctypes.c_int64 * k)(*mods), _ptr(out), B, N, D, k, d_x0.stride(1),
+                                                             _stream()), "cd360_textgrad_token_rows_f32")
+    return out

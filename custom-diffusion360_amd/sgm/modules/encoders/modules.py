@@ -15,7 +15,11 @@ file: weights arrive through load_state_dict.  Two routes, as everywhere in this
   anything else (CPU, fp32, ...)         a plain torch restatement of the same computation, in the parameters' dtype.
 
 A HIP-route embedder under a tape (grad enabled and a parameter that requires grad -- with `modifier_token` the token table does) raises
-NotImplementedError: there is no backward.  Packed weights go through cd360.derived.derived and follow its one invalidation rule.
+NotImplementedError: there is no backward for the tower's own parameters.  The one backward that exists is opt-in: an embedder that
+cd360.finetune.train_tokens marked (`token_rows`: its k modifier rows as a leaf parameter of their own, the table itself frozen) runs, with
+grad enabled, through cd360.grad.TextTowerFn on the HIP route (the same forward launches; the backward on libcd360_textgrad.so) and embeds
+from torch.cat([table[:-k].detach(), rows]) on the torch route.  Packed weights go through cd360.derived.derived and follow its one
+invalidation rule.
 
 Text input: no tokenizer vocabulary ships with this package.  `text` is an int64 tensor [B, max_length] of token ids, or a list of strings
 together with a `tokenizer=` callable (constructor argument) that returns such a tensor."""
@@ -267,8 +271,10 @@ def _layer_torch(x, L: _Layer, heads: int, kind: int):
     return x + F.linear(_act_torch(h, kind), L.fc2.weight, L.fc2.bias)
 
 
-def _layer_hip(x, stats, L: _Layer, heads: int, kind: int, want_stats: bool):
-    """The six launches of a layer.  x [B, N, D] bf16 and its row statistics -> (x', statistics of x' | None)."""
+def _layer_hip(x, stats, L: _Layer, heads: int, kind: int, want_stats: bool, tape: Optional[list] = None):
+    """The six launches of a layer.  x [B, N, D] bf16 and its row statistics -> (x', statistics of x' | None).  `tape` (the training
+    forward of cd360.grad.TextTowerFn): the same launches with the activation written beside its input, not over it, and what the
+    backward reads -- the layer's input, the merged q|k|v projection, the stream behind the attention, the pre-activation -- appended."""
     D = x.shape[-1]
     ws, bs = L.qkv
     wq, wsq, cbq = derived(L.owner, "_cd360_qkv", (*ws, *bs, L.ln1.weight, L.ln1.bias),
@@ -280,9 +286,14 @@ def _layer_hip(x, stats, L: _Layer, heads: int, kind: int, want_stats: bool):
                                       L.fc2.weight.detach().contiguous(), L.fc2.bias.detach().float().contiguous()))
     qkv = ops.gemm(x, wq, bias=cbq, ln=(stats, wsq, LN_EPS))
     o = ops.causal_attention(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], heads)
+    x_in = x
     x, stats = ops.gemm(o, wo, bias=bo, res=x, want_stats=True)
     h = ops.gemm(x, w1, bias=cb1, ln=(stats, ws1, LN_EPS))
-    ops.text_activation(h, kind, out=h)
+    if tape is None:
+        ops.text_activation(h, kind, out=h)
+    else:
+        tape.append((x_in, qkv, x, h))
+        h = ops.text_activation(h, kind)
     if want_stats:
         return ops.gemm(h, w2, bias=b2, res=x, want_stats=True)
     return ops.gemm(h, w2, bias=b2, res=x), None
@@ -338,19 +349,53 @@ class _TextTower(AbstractEmbModel):
                                  f"{self.heads} heads, {self.max_length} tokens")
         return True
 
-    def _run(self, ids, want_penultimate: bool = False):
-        """ids on the device -> (output of the last layer, input of the last layer | None, hip) -- before any final LayerNorm."""
+    def _train_rows(self):
+        """The trainable modifier rows of an embedder that cd360.finetune.train_tokens marked, when a tape is wanted (grad enabled); else
+        None and nothing changes.  The rows are first copied into the last k rows of the token table (no_grad, in place: the version
+        counter moves), so the table every route reads holds what the optimiser last wrote."""
+        rows = self.__dict__.get("token_rows")
+        if rows is None or not (torch.is_grad_enabled() and rows.requires_grad):
+            return None
+        tok = self._tables()[0]
+        with torch.no_grad():
+            tok[tok.shape[0] - rows.shape[0]:].copy_(rows)
+        return rows
+
+    def _hip_outputs(self, ids, wants, tape: Optional[list] = None):
+        """The HIP route's results by name, in the order of `wants`: "pen" (input of the last layer), "last_ln" / "pen_ln" (final LayerNorm
+        of the last layer's output / input), "pooled".  One walk; with `tape` it is the training forward of cd360.grad.TextTowerFn, and
+        the output of the last layer (before the final LayerNorm) is appended behind the layers' entries."""
+        last, pen, hip = self._run(ids, want_penultimate=True, tape=tape)
+        assert hip
+        if tape is not None:
+            tape.append(last)
+        out = {"pen": pen}
+        if "last_ln" in wants or "pooled" in wants:
+            out["last_ln"] = self._ln(last, True)
+        if "pen_ln" in wants:
+            out["pen_ln"] = self._ln(pen, True)
+        if "pooled" in wants:
+            out["pooled"] = self.pool(out["last_ln"], ids, True)
+        return [out[w] for w in wants]
+
+    def _run(self, ids, want_penultimate: bool = False, rows=None, tape: Optional[list] = None):
+        """ids on the device -> (output of the last layer, input of the last layer | None, hip) -- before any final LayerNorm.  `rows`
+        (torch route of a marked embedder): the trainable modifier rows, embedded from torch.cat([table[:-k].detach(), rows]), which is
+        the reference's (1 - indices) * x.detach() + indices * x."""
         tok, pos = self._tables()
         layers = self._layers()
         hip = self._hip_route()
         pen = None
         if hip:
+            assert rows is None
             x, stats = ops.text_embed(ids, tok.detach(), pos.detach()[:ids.shape[1]].contiguous(), want_stats=True)
             for i, L in enumerate(layers):
                 if i == len(layers) - 1:
                     pen = x
-                x, stats = _layer_hip(x, stats, L, self.heads, self.act_kind, want_stats=i < len(layers) - 1)
+                x, stats = _layer_hip(x, stats, L, self.heads, self.act_kind, want_stats=i < len(layers) - 1, tape=tape)
         else:
+            if rows is not None:
+                tok = torch.cat([tok.detach()[:tok.shape[0] - rows.shape[0]], rows.to(tok.dtype)], 0)
             x = F.embedding(ids, tok) + pos[:ids.shape[1]]
             for i, L in enumerate(layers):
                 if i == len(layers) - 1:
@@ -470,7 +515,11 @@ class FrozenCLIPEmbedder(_TextTower):
 
     def forward(self, text):
         _, ids = self._tokens(text)
-        x, _, hip = self._run(ids)
+        rows = self._train_rows()
+        if rows is not None and self._hip_route():
+            from cd360 import grad
+            return grad.TextTowerFn.apply(rows, self, ids, ("last_ln",))[0]
+        x, _, hip = self._run(ids, rows=rows)
         return self._ln(x, hip)
 
 
@@ -560,7 +609,13 @@ class FrozenOpenCLIPEmbedder(_TextTower):
         return x[torch.arange(x.shape[0], device=x.device), ids.argmax(dim=-1)] @ proj
 
     def encode_with_transformer(self, ids):
-        last, pen, hip = self._run(ids, want_penultimate=True)
+        rows = self._train_rows()
+        if rows is not None and self._hip_route():
+            from cd360 import grad
+            if self.legacy:
+                return grad.TextTowerFn.apply(rows, self, ids, ("last_ln" if self.layer == "last" else "pen_ln",))[0]
+            return dict(zip(("penultimate", "last", "pooled"), grad.TextTowerFn.apply(rows, self, ids, ("pen", "last_ln", "pooled"))))
+        last, pen, hip = self._run(ids, want_penultimate=True, rows=rows)
         if self.legacy:
             return self._ln(last if self.layer == "last" else pen, hip)
         z = {"penultimate": pen, "last": self._ln(last, hip)}
