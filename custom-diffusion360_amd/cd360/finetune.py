@@ -13,6 +13,9 @@ UNet module that an engine (or a test) calls.
   MasterAdamW / train_step  diffusion.py:226-262   one optimisation step of the fine-tuning loop: UNet forward (HIP kernels), the four
                                                    loss terms, backward (HIP backward kernels via cd360/grad.py), AdamW on fp32 master
                                                    copies of the trainable (bf16) parameters
+  NoiseStage / train_step_latents / encode_batch   loss.py:146-168, denoiser.py:22-44, diffusion.py:238-249   the same step from CLEAN
+                                                   latents and a seed: sigma draws, noising and scaling in front of the UNet and the l2
+                                                   term behind it as HIP launches (include/train/cd360_train.h), graph-safe
 
 The all-gather in harvest_references is the one exchange step of the training side: each rank holds the features of its share
 of the reference images ([N_local, hw, C] per pose block, 12 blocks) and every rank needs all of them in dataset order
@@ -558,6 +561,182 @@ def train_step(unet: torch.nn.Module, loss_fn, optimizer, *, noised, timesteps, 
     return total.detach(), logged
 
 
+# ---------------------------------------------------------------- a step from clean latents
+class Staged:
+    """What NoiseStage.__call__ returns: views of the stage's buffers, valid until its next call.  x_t [B, 4, H, W] fp32 (the noised
+    target); x_in (x_t * c_in) and input_ref ([B, n, 4, H, W] or None: the twice-noised reference views * c_in_ref) in the stage's dtype;
+    timesteps / sigmas_ref int64 [B] (sigma_to_idx of sigma / sigma_ref: what the UNet embeds); scalars [B, 12] fp32 (cd360._train: sigma,
+    w, c_skip, c_out, c_in, sigma_ref, c_in_ref, off_tgt, off_ref); step_used int32 [1]."""
+
+    def __init__(self, stage, x_t, x_in, timesteps, input_ref, sigmas_ref, scalars, step_used):
+        self.stage, self.x_t, self.x_in, self.timesteps, self.input_ref, self.sigmas_ref = stage, x_t, x_in, timesteps, input_ref, sigmas_ref
+        self.scalars, self.step_used = scalars, step_used
+
+    def l2(self, eps, x0, mask=None):
+        from . import ops
+        return ops.train_l2(eps, self.x_t, x0, self.scalars, mask)
+
+
+class NoiseStage:
+    """The front and the l2 tail of a training step on the device (include/train/cd360_train.h): what StandardDiffusionLossImgRef.__call__
+    and DiscreteDenoiser do around the network -- the sigma draws, the target and offset noise, the two noisings of the reference views,
+    c_in / c_out / w, the drop_im zeroing of shared_step -- in two launches in front of the UNet and one (plus one backward) behind it.
+    Every random number is a pure function of (seed, stream id of the sample, step, channel, pixel): a hipGraph replay, an eager call and
+    any split of the samples over ranks draw the same bits (give each sample its global index as stream id).
+
+    Reads loss_fn.sigma_sampler, loss_fn.sigma_sampler_ref, loss_fn.offset_noise_level and denoiser.sigmas (whose device is the stage's).
+    ValueError for anything but CubicSampling / DiscreteSampling, EpsScaling, EpsWeighting and type "l2", and for a loss without a reference sampler:
+    a reference index is always drawn.  The reference's denoiser snaps the target sigma to its own table before c_in / c_out; the kernels
+    take the sampler's sigma as it is, so a target sampler whose table does not lie ON the denoiser's (possibly_quantize_sigma(s) != s for
+    an entry; the shipped config uses the same 1000-entry table for both) is refused too.  sigma_ref is not snapped by the reference either.
+
+    The stage owns the device seed, the stream ids, the step counter and every output buffer (allocated on the first call of a shape, then
+    reused), so a captured call keeps reading and writing the same memory: set_step / reseed / set_streams rewrite them in place and reach
+    the replays.  A call draws at the step counter's value and, with advance=True (the default), leaves it one higher -- on the device, so
+    a replay advances it too.  dtype: what x_in and input_ref are written in -- the dtype UNetModel.forward casts its inputs to."""
+
+    def __init__(self, denoiser, loss_fn, seed: int, streams=None, dtype=torch.bfloat16):
+        from sgm.modules.diffusionmodules.sigma_sampling import CubicSampling, DiscreteSampling
+        from . import ops
+        from .sampler import EpsScaling, EpsWeighting, seed_words
+
+        def named(obj, cls):  # the package's class, or the class of that name an engine instantiated from the YAML target
+            return isinstance(obj, cls) or type(obj).__name__ == cls.__name__
+
+        def sampler(s, what):
+            if s is None:
+                raise ValueError(f"NoiseStage: the loss has no {what} (sigma_sampler_config_ref = None): a reference index is always drawn")
+            if named(s, CubicSampling):
+                return ops.TRAIN_CUBIC, 0
+            if named(s, DiscreteSampling):
+                return ops.TRAIN_DISCRETE, int(s.num_idx_start)
+            raise ValueError(f"NoiseStage: {what} is a {type(s).__name__}; CubicSampling and DiscreteSampling are served")
+
+        if not named(getattr(denoiser, "scaling", None), EpsScaling):
+            raise ValueError(f"NoiseStage: the denoiser's scaling is a {type(getattr(denoiser, 'scaling', None)).__name__}; EpsScaling is served")
+        if not named(getattr(denoiser, "weighting", None), EpsWeighting):
+            raise ValueError(f"NoiseStage: the denoiser's weighting is a {type(getattr(denoiser, 'weighting', None)).__name__}; EpsWeighting is served")
+        if getattr(loss_fn, "type", "l2") != "l2":
+            raise ValueError(f"NoiseStage: the loss is of type {loss_fn.type!r}; the stage's tail is the l2 term (stage.l2 stands in for get_loss)")
+        self.tgt_kind, self.tgt_start = sampler(loss_fn.sigma_sampler, "sigma_sampler")
+        self.ref_kind, self.ref_start = sampler(getattr(loss_fn, "sigma_sampler_ref", None), "sigma_sampler_ref")
+        self.level = float(loss_fn.offset_noise_level)
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"NoiseStage: dtype {dtype}; fp32 and bf16 are served")
+        self.dtype = dtype
+        table = denoiser.sigmas.detach()
+        tgt = loss_fn.sigma_sampler.sigmas.detach().to("cpu", torch.float32)
+        grid = table.to("cpu", torch.float32)
+        if not torch.equal(grid[(tgt[None, :] - grid[:, None]).abs().argmin(0)], tgt):
+            raise ValueError("NoiseStage: the target sampler's sigmas do not lie on the denoiser's table (the reference would snap them before c_in / c_out)")
+        if not table.is_cuda:
+            raise ops.Cd360Error("the training stage runs only on the GPU; the denoiser's sigmas are a CPU tensor")
+        dev = self.device = table.device
+        f32 = lambda t: t.detach().to(dev, torch.float32).contiguous().clone()
+        self.table, self.tgt_table, self.ref_table = f32(table), f32(loss_fn.sigma_sampler.sigmas), f32(loss_fn.sigma_sampler_ref.sigmas)
+        self._seed_words = seed_words
+        self.seed = torch.tensor([seed_words(seed)], dtype=torch.int64, device=dev)
+        self.step = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.streams = None if streams is None else torch.tensor([int(v) for v in streams], dtype=torch.int32, device=dev)
+        self._buffers, self._last = {}, None
+
+    # ---- the state a captured call reads: rewritten in place
+    def set_step(self, k: int) -> None:
+        self.step.fill_(((int(k) + 2 ** 31) % 2 ** 32) - 2 ** 31)  # the counter's word is the low 32 bits
+
+    def reseed(self, seed: int) -> None:
+        self.seed.fill_(self._seed_words(seed))
+
+    def set_streams(self, ids) -> None:
+        ids = [int(v) for v in ids]
+        if self.streams is None or self.streams.numel() != len(ids):
+            raise ValueError("set_streams: the stage was built with "
+                             f"{'no stream ids' if self.streams is None else f'{self.streams.numel()} stream ids'}, got {len(ids)} (a new stage is needed)")
+        self.streams.copy_(torch.tensor(ids, dtype=torch.int32))
+
+    def _gpu(self, *ts):
+        from . import ops
+        for t in ts:
+            if t is not None and not t.is_cuda:
+                raise ops.Cd360Error("the training stage runs only on the GPU; got a CPU tensor")
+
+    def __call__(self, x0, x_ref=None, drop_im=None, advance: bool = True) -> Staged:
+        """x0 [B, 4, H, W] fp32 clean latents; x_ref [B, n, 4, H, W] fp32 clean reference latents or None; drop_im [B] fp32 or None (1 = the
+        sample keeps its reference views, 0 = they are zeroed before the noising)."""
+        from . import ops
+        self._gpu(x0, x_ref, drop_im)
+        B = x0.shape[0]
+        if self.streams is not None and self.streams.numel() != B:
+            raise ValueError(f"{self.streams.numel()} noise stream ids for {B} samples")
+        key = (tuple(x0.shape), None if x_ref is None else tuple(x_ref.shape))
+        buf = self._buffers.get(key)
+        if buf is None:
+            dev = self.device
+            buf = self._buffers[key] = dict(
+                scalars=(torch.zeros((B, ops.TRAIN_ROW), dtype=torch.float32, device=dev), torch.zeros((B,), dtype=torch.int64, device=dev),
+                         torch.zeros((B,), dtype=torch.int64, device=dev), torch.zeros((1,), dtype=torch.int32, device=dev)),
+                noised=(torch.zeros(x0.shape, dtype=torch.float32, device=dev), torch.zeros(x0.shape, dtype=self.dtype, device=dev),
+                        None if x_ref is None else torch.zeros(x_ref.shape, dtype=self.dtype, device=dev)))
+        rows, timesteps, ref_idx, step_used = ops.train_sigmas(self.table, self.tgt_table, self.tgt_kind, self.tgt_start, self.ref_table, self.ref_kind,
+                                                               self.ref_start, self.seed, self.streams, self.step, B, advance=advance, out=buf["scalars"])
+        drop = None if drop_im is None else drop_im.detach().float().contiguous()
+        x_t, x_in, xr_in = ops.train_noise(x0.detach(), None if x_ref is None else x_ref.detach(), drop, rows, self.seed, self.streams, step_used,
+                                           self.level, dtype=self.dtype, out=buf["noised"])
+        self._last = Staged(self, x_t, x_in, timesteps, xr_in, ref_idx, rows, step_used)
+        return self._last
+
+    def l2(self, eps, x0, mask=None):
+        """The l2 term [B] of the LAST call's noising from the network's output eps (any layout, fp32 or bf16); differentiable in eps."""
+        if self._last is None:
+            raise ValueError("NoiseStage.l2: the stage has not been called yet")
+        self._gpu(eps, x0, mask)
+        return self._last.l2(eps, x0, mask)
+
+
+def encode_batch(first_stage, x, x_ref, seed: int, step: int, streams=None):
+    """The two encode_first_stage calls of shared_step (sgm/models/diffusion.py:241-245) on cd360.images.FirstStage: x [B, 3, H, W] ->
+    x0 [B, 4, H / 8, W / 8]; x_ref [B, n, 3, H, W] or None -> [B, n, 4, H / 8, W / 8].  The posterior samples are drawn at draw = step.
+    streams: one id per sample, the ids NoiseStage is given (the sample's index in the data set, so that the encoder's noise too is the
+    sample's own on any split of the batch over ranks); None = the row's index in THIS batch, which is right for one process only: ranks
+    that pass None draw the same noise for different images.  Sample s encodes its target in noise stream s (1 + n) and its view v in
+    stream s (1 + n) + 1 + v, so no two images of a step share their noise.  Runs outside a captured step: the encoder allocates."""
+    B = x.shape[0]
+    n = 0 if x_ref is None else x_ref.shape[1]
+    ids = list(range(B)) if streams is None else [int(s) for s in streams]
+    if len(ids) != B:
+        raise ValueError(f"{len(ids)} noise stream ids for {B} samples")
+    x0 = first_stage.encode(x, seed, step, streams=[s * (1 + n) for s in ids])
+    if x_ref is None:
+        return x0, None
+    z = first_stage.encode(x_ref.reshape(B * n, *x_ref.shape[2:]), seed, step, streams=[s * (1 + n) + 1 + v for s in ids for v in range(n)])
+    return x0, z.reshape(B, n, *z.shape[1:])
+
+
+def train_step_latents(unet: torch.nn.Module, loss_fn, optimizer, stage: NoiseStage, *, x0, x_ref, context, y, pose, target_rgb, mask, opacity,
+                       drop_im=None, mask_ref=None, as_tensors: bool = False, **loss_kw):
+    """One step of the fine-tuning loop from CLEAN latents: stage (sigma draws, noising, scaling: NoiseStage) -> UNet -> the l2 term
+    (stage.l2) and the render terms (StandardDiffusionLossImgRef.render_terms) -> the lambda-weighted total -> backward -> optimiser step.
+    With FirstStage.encode (encode_batch) and train_tokens this is training_step of the reference's engine.  The step counter of the stage
+    advances by one.  Returns as train_step does."""
+    optimizer.zero_grad()
+    if _has_adapters(unet):
+        from . import ops
+        ops.dropout_tick(x0.device)
+    st = stage(x0, x_ref, drop_im)
+    out, fgs, alphas, rgbs = unet(st.x_in, timesteps=st.timesteps, context=context, y=y, pose=pose, input_ref=st.input_ref, sigmas_ref=st.sigmas_ref,
+                                  mask_ref=mask_ref)
+    l2 = stage.l2(out, x0, mask)
+    lfg, lbg, lrgb = loss_fn.render_terms(fgs, rgbs, target_rgb, mask, opacity, alphas)
+    if drop_im is None:
+        drop_im = torch.ones(x0.shape[0], device=x0.device)
+    total, logged = combine_losses(l2, lfg, lbg, lrgb, drop_im, as_tensors=True, **loss_kw)
+    total.backward()
+    optimizer.step()
+    if not as_tensors:
+        logged = {k: float(v) for k, v in logged.items()}
+    return total.detach(), logged
+
+
 class GraphedTrainStep:
     """train_step captured ONCE into a hipGraph and replayed: forward, loss, backward and the optimiser step of BASELINE config 4 are
     ~6400 kernel launches and ~16000 torch operator calls per step -- host work that takes longer than the kernels run (DESIGN.md section 6b);
@@ -571,13 +750,24 @@ class GraphedTrainStep:
     their patch jitter from the device generator too; (3) unless the optimiser is LIVE (MasterAdamW(max_grad_norm= / ema_decay= / live=True)),
     lr and weight_decay are frozen into the graph at capture time -- an LR scheduler that edits `optimizer.param_groups` then has no effect
     on replays (re-capture to change them).  A live optimiser reads both from a device table that __call__ refreshes (sync_hyper, outside
-    the graph) before every replay: schedules reach the replays."""
+    the graph) before every replay: schedules reach the replays.
+    stage=NoiseStage(...): the captured step is train_step_latents -- `batch` then holds ITS keywords (x0, x_ref, context, y, pose,
+    target_rgb, mask, opacity, drop_im, mask_ref: clean latents instead of noised ones) and the stage's launches are graph nodes, the sigma
+    draw with advance on: replay k after the capture draws at step counter + k, with no host work, and stage.set_step / reseed /
+    set_streams between replays reach the next one.  Every warm-up step is a real step and advances the stage's step counter by one (the
+    capture itself only records: it draws nothing and advances nothing), so after construction the counter stands `warmup` higher than
+    before; warmup_restore=True puts it back to its value from before the warm-up.  stage=None (the default) changes nothing:
+    no buffer, no launch, no graph node."""
 
     def __init__(self, unet: torch.nn.Module, loss_fn, optimizer: "MasterAdamW", batch: dict, warmup: int = 3, warmup_restore: bool = False,
-                 weight_prefetch: bool = False, **loss_kw):
+                 weight_prefetch: bool = False, stage: Optional["NoiseStage"] = None, **loss_kw):
         if not optimizer.capturable:
             raise ValueError("GraphedTrainStep: the torch fall-back of MasterAdamW must be built with capturable=True (the fused path is as it is)")
-        self.unet, self.loss_fn, self.optimizer, self.loss_kw = unet, loss_fn, optimizer, loss_kw
+        self.unet, self.loss_fn, self.optimizer, self.loss_kw, self.stage = unet, loss_fn, optimizer, loss_kw, stage
+        if stage is None:
+            step_fn = train_step
+        else:
+            step_fn = lambda unet, loss_fn, optimizer, **kw: train_step_latents(unet, loss_fn, optimizer, stage, **kw)
         for m in unet.modules():
             if hasattr(m, "device_rng"):
                 m.device_rng = True
@@ -590,8 +780,11 @@ class GraphedTrainStep:
             if warmup_restore and optimizer.fused:
                 saved = ([p.detach().clone() for p in optimizer.params], optimizer._master.clone(), optimizer.exp_avg.clone(),
                          optimizer.exp_avg_sq.clone(), optimizer.steps.clone(), None if optimizer._ema is None else optimizer._ema.clone())
+            stage_step = stage.step.clone() if warmup_restore and stage is not None else None
             for _ in range(warmup):
-                train_step(unet, loss_fn, optimizer, as_tensors=True, **self.static, **loss_kw)
+                step_fn(unet, loss_fn, optimizer, as_tensors=True, **self.static, **loss_kw)
+            if stage_step is not None:
+                stage.step.copy_(stage_step)
             if saved is not None:
                 with torch.no_grad():
                     for p, q in zip(optimizer.params, saved[0]):
@@ -614,7 +807,7 @@ class GraphedTrainStep:
             pf = WeightPrefetcher(next(unet.parameters()).device)
         with torch.cuda.graph(self.graph, capture_error_mode=mode):
             with pf:
-                self.total, self.logged = train_step(unet, loss_fn, optimizer, as_tensors=True, **self.static, **loss_kw)
+                self.total, self.logged = step_fn(unet, loss_fn, optimizer, as_tensors=True, **self.static, **loss_kw)
         memo.new_epoch()
 
     @staticmethod

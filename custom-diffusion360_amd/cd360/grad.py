@@ -321,6 +321,23 @@ class RenderLossFn(torch.autograd.Function):
         return d_fg, d_al, d_rgb, None, None, None, None, None
 
 
+class TrainL2Fn(torch.autograd.Function):
+    """ops.train_l2: the l2 term of the loss from the network's output (loss.py:183-187 of the reference behind DiscreteDenoiser's
+    eps * c_out + x_t * c_skip) as one kernel each way (cd360_train_l2_f32, cd360_train_l2_bwd_f32); x_t, x0, the scalar rows and the mask
+    are constants of the step.  The gradient has eps's dtype and layout."""
+
+    @staticmethod
+    def forward(ctx, eps, x_t, x0, rows, mask):
+        loss, den = ops._train_l2_fwd(eps, x_t, x0, rows, mask)
+        ctx.save_for_backward(eps, x_t, x0, rows, mask, den)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        eps, x_t, x0, rows, mask, den = ctx.saved_tensors
+        return ops.train_l2_bwd(eps, x_t, x0, rows, mask, den, g), None, None, None, None
+
+
 class RowDot4Fn(torch.autograd.Function):
     """ops.rowdot4 (FeatureNeRFEncoding.decoder, Linear(C -> 4, no bias), nerfsd_pytorch3d.py:49-51,160); backward =
     cd360_rowdot4_bwd_bf16 (dh = d w in one pass, dw = d^T h as a slab-wise column reduction)."""

@@ -1934,6 +1934,153 @@ def mask_blend(x: torch.Tensor, known: torch.Tensor, mask: torch.Tensor, sigma_n
     return x
 
 
+# ----------------------------------------------------------------------------------------------- the ends of a training step (include/train/cd360_train.h)
+# libcd360_train.so through cd360/_train.py.  Refusals as above: ValueError before the device check and before the library is loaded.
+TRAIN_ROW = 12  # CD360_TRAIN_ROW
+TRAIN_CUBIC, TRAIN_DISCRETE = 0, 1
+
+
+def _sigma_table(t: torch.Tensor, name: str) -> None:
+    _refuse(not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.ndim != 1 or t.numel() == 0 or not t.is_contiguous(),
+            f"{name}: a contiguous fp32 vector of sigmas is needed")
+
+
+def _sampler_args(kind: int, start: int, table: torch.Tensor, name: str) -> None:
+    _refuse(kind not in (TRAIN_CUBIC, TRAIN_DISCRETE), f"{name}: kind {kind} is neither cubic (0) nor discrete (1)")
+    _refuse(kind == TRAIN_DISCRETE and not 0 <= start < table.numel(), f"{name}: num_idx_start {start} outside [0, {table.numel()})")
+
+
+def train_sigmas(table: torch.Tensor, tgt_table: torch.Tensor, tgt_kind: int, tgt_start: int, ref_table: torch.Tensor, ref_kind: int, ref_start: int,
+                 seed: torch.Tensor, streams: Optional[torch.Tensor], step: torch.Tensor, B: int, advance: bool = False, out=None):
+    """The per-sample draws and scalars of a training step (cd360_train_sigmas_f32) -> (rows [B, TRAIN_ROW] fp32, timesteps int64 [B],
+    sigmas_ref_idx int64 [B], step_used int32 [1]).  table: the denoiser's sigmas; tgt_table / ref_table: the samplers' tables with their
+    kind (TRAIN_CUBIC / TRAIN_DISCRETE) and num_idx_start; seed device int64[1]; streams device int32[B] or None; step device int32[1],
+    incremented on the device when `advance`.  A row holds sigma, w, c_skip, c_out, c_in, sigma_ref, c_in_ref, off_tgt, off_ref (cd360._train).
+    out: the four result buffers to write instead of fresh ones."""
+    from . import _train
+    _refuse(B <= 0, f"B must be positive, got {B}")
+    for t, name in ((table, "table"), (tgt_table, "tgt_table"), (ref_table, "ref_table")):
+        _sigma_table(t, name)
+    _sampler_args(tgt_kind, tgt_start, tgt_table, "sigma_sampler")
+    _sampler_args(ref_kind, ref_start, ref_table, "sigma_sampler_ref")
+    _seed_args(seed, streams, B)
+    _step_arg(step)
+    _need_gpu(table, tgt_table, ref_table, seed, streams, step)
+    dev = seed.device
+    if out is None:
+        out = (torch.empty((B, TRAIN_ROW), dtype=torch.float32, device=dev), torch.empty((B,), dtype=torch.int64, device=dev),
+               torch.empty((B,), dtype=torch.int64, device=dev), torch.empty((1,), dtype=torch.int32, device=dev))
+    rows, timesteps, ref_idx, step_used = out
+    _f32_tensor(rows, (B, TRAIN_ROW), "rows")
+    _refuse(any(t.dtype != torch.int64 or tuple(t.shape) != (B,) or not t.is_contiguous() for t in (timesteps, ref_idx)),
+            f"timesteps, sigmas_ref_idx: contiguous int64 [{B}] are needed")
+    _step_arg(step_used)
+    _need_gpu(rows, timesteps, ref_idx, step_used)
+    check(_train.load().cd360_train_sigmas_f32(_ptr(table), table.numel(), _ptr(tgt_table), tgt_table.numel(), tgt_kind, tgt_start, _ptr(ref_table),
+                                               ref_table.numel(), ref_kind, ref_start, _ptr(seed), _ptr(streams), _ptr(step), int(bool(advance)),
+                                               _ptr(rows), _ptr(timesteps), _ptr(ref_idx), _ptr(step_used), B, _stream()), "cd360_train_sigmas_f32")
+    return rows, timesteps, ref_idx, step_used
+
+
+def train_noise(x0: torch.Tensor, x_ref: Optional[torch.Tensor], drop_im: Optional[torch.Tensor], rows: torch.Tensor, seed: torch.Tensor,
+                streams: Optional[torch.Tensor], step_used: torch.Tensor, level: float, dtype=torch.float32, out=None):
+    """Noise the target latent and the reference views and scale them for the network (cd360_train_noise_f32) -> (x_t fp32, x_in, xr_in |
+    None), x_in and xr_in in `dtype` (fp32 or bf16).  x0 [B, 4, H, W] fp32; x_ref [B, n, 4, H, W] fp32 or None; drop_im [B] fp32 or None;
+    rows, step_used as train_sigmas returned them; level = offset_noise_level.  out: (x_t, x_in, xr_in) to write instead of fresh ones."""
+    from . import _train
+    _refuse(not isinstance(x0, torch.Tensor) or x0.ndim != 4 or x0.shape[1] != 4, f"x0: [B, 4, H, W] is needed, got {tuple(getattr(x0, 'shape', ()))}")
+    B, _, H, W = x0.shape
+    _refuse(B <= 0 or H * W <= 0, f"x0 is empty: {tuple(x0.shape)}")
+    _f32_tensor(x0, x0.shape, "x0")
+    n = 0
+    if x_ref is not None:
+        _refuse(x_ref.ndim != 5 or x_ref.shape[0] != B or x_ref.shape[1] <= 0 or tuple(x_ref.shape[2:]) != (4, H, W),
+                f"x_ref: [{B}, n, 4, {H}, {W}] is needed, got {tuple(x_ref.shape)}")
+        n = x_ref.shape[1]
+        _refuse(n * H * W > 1 << 32, f"x_ref: n * H * W = {n * H * W} > 2^32 (the pixel is one 32-bit counter word)")
+        _f32_tensor(x_ref, x_ref.shape, "x_ref")
+    _refuse(H * W > 1 << 32, f"x0: H * W = {H * W} > 2^32")
+    if drop_im is not None:
+        _f32_tensor(drop_im, (B,), "drop_im")
+    _f32_tensor(rows, (B, TRAIN_ROW), "rows")
+    _seed_args(seed, streams, B)
+    _step_arg(step_used)
+    _refuse(dtype not in (torch.float32, torch.bfloat16), f"dtype: fp32 or bf16, got {dtype}")
+    _refuse(not (0.0 <= float(level) < float("inf")), f"level = {level}: a finite value >= 0 is needed")
+    _need_gpu(x0, x_ref, drop_im, rows, seed, streams, step_used)
+    if out is None:
+        out = (torch.empty(x0.shape, dtype=torch.float32, device=x0.device), torch.empty(x0.shape, dtype=dtype, device=x0.device),
+               None if x_ref is None else torch.empty(x_ref.shape, dtype=dtype, device=x0.device))
+    x_t, x_in, xr_in = out
+    _f32_tensor(x_t, x0.shape, "x_t")
+    _refuse(x_in.dtype != dtype or tuple(x_in.shape) != tuple(x0.shape) or not x_in.is_contiguous(), f"x_in: contiguous {dtype} {tuple(x0.shape)} is needed")
+    if x_ref is not None:
+        _refuse(xr_in is None or xr_in.dtype != dtype or tuple(xr_in.shape) != tuple(x_ref.shape) or not xr_in.is_contiguous(),
+                f"xr_in: contiguous {dtype} {tuple(x_ref.shape)} is needed")
+    _need_gpu(x_t, x_in, xr_in)
+    check(_train.load().cd360_train_noise_f32(_ptr(x0), _ptr(x_ref), _ptr(drop_im), _ptr(rows), _ptr(seed), _ptr(streams), _ptr(step_used), float(level),
+                                              _ptr(x_t), _ptr(x_in), _ptr(xr_in) if x_ref is not None else None, int(dtype == torch.bfloat16), B, n,
+                                              H * W, _stream()), "cd360_train_noise_f32")
+    return x_t, x_in, (xr_in if x_ref is not None else None)
+
+
+def _train_l2_args(eps, x_t, x0, rows, mask):
+    _refuse(not isinstance(eps, torch.Tensor) or eps.ndim != 4 or eps.shape[1] != 4, f"eps: [B, 4, H, W] is needed, got {tuple(getattr(eps, 'shape', ()))}")
+    _refuse(eps.dtype not in (torch.float32, torch.bfloat16), f"eps: fp32 or bf16, got {eps.dtype}")
+    B, _, H, W = eps.shape
+    _refuse(B <= 0 or H * W <= 0, f"eps is empty: {tuple(eps.shape)}")
+    _refuse(any(s < 0 for s in eps.stride()), "eps: negative strides")
+    _f32_tensor(x_t, eps.shape, "x_t")
+    _f32_tensor(x0, eps.shape, "x0")
+    _f32_tensor(rows, (B, TRAIN_ROW), "rows")
+    if mask is not None:
+        _f32_tensor(mask, (B, 1, H, W), "mask")
+    return B, H, W
+
+
+def _strides4(t: torch.Tensor):
+    return (ctypes.c_int64 * 4)(*t.stride())
+
+
+def train_l2(eps: torch.Tensor, x_t: torch.Tensor, x0: torch.Tensor, rows: torch.Tensor, mask: Optional[torch.Tensor]) -> torch.Tensor:
+    """The l2 term of the loss from the network's output -> [B] fp32 (cd360_train_l2_f32): D = eps c_out + x_t c_skip, w (D - x0)^2 summed
+    over the mask and divided by sum(mask) + 1e-6, or the mean without a mask (loss.py:183-187 of the reference).  eps [B, 4, H, W] fp32 or
+    bf16 in ANY layout (read by its strides, no copy); x_t, x0 fp32 contiguous; rows as train_sigmas returned them; mask [B, 1, H, W] fp32
+    or None.  Differentiable with respect to eps (grad.TrainL2Fn); the same bits on every run."""
+    if _wants_grad(eps):
+        from . import grad
+        return grad.TrainL2Fn.apply(eps, x_t, x0, rows, mask)
+    return _train_l2_fwd(eps, x_t, x0, rows, mask)[0]
+
+
+def _train_l2_fwd(eps, x_t, x0, rows, mask):
+    """-> (loss [B], den [B]): den is what the backward divides by."""
+    from . import _train
+    B, H, W = _train_l2_args(eps, x_t, x0, rows, mask)
+    eps = eps.detach()
+    _need_gpu(eps, x_t, x0, rows, mask)
+    loss = torch.empty((B,), dtype=torch.float32, device=eps.device)
+    den = torch.empty((B,), dtype=torch.float32, device=eps.device)
+    check(_train.load().cd360_train_l2_f32(_ptr(eps), int(eps.dtype == torch.bfloat16), _strides4(eps), _ptr(x_t), _ptr(x0), _ptr(rows), _ptr(mask),
+                                           _ptr(loss), _ptr(den), B, H, W, _stream()), "cd360_train_l2_f32")
+    return loss, den
+
+
+def train_l2_bwd(eps, x_t, x0, rows, mask, den, g) -> torch.Tensor:
+    """-> d_eps in eps's dtype and layout: g[b] 2 w err c_out [mask] / den[b], an exact 0 where g[b] == 0 (cd360_train_l2_bwd_f32)."""
+    from . import _train
+    B, H, W = _train_l2_args(eps, x_t, x0, rows, mask)
+    eps = eps.detach()
+    _f32_tensor(den, (B,), "den")
+    g = g.detach().float().contiguous()
+    _refuse(tuple(g.shape) != (B,), f"g: [{B}] is needed, got {tuple(g.shape)}")
+    _need_gpu(eps, x_t, x0, rows, mask, den, g)
+    d_eps = torch.empty_like(eps)
+    check(_train.load().cd360_train_l2_bwd_f32(_ptr(eps), int(eps.dtype == torch.bfloat16), _strides4(eps), _ptr(x_t), _ptr(x0), _ptr(rows), _ptr(mask),
+                                               _ptr(den), _ptr(g), _ptr(d_eps), _strides4(d_eps), B, H, W, _stream()), "cd360_train_l2_bwd_f32")
+    return d_eps
+
+
 # ----------------------------------------------------------------------------------------------- rank-r adapters (add_lora=True)
 LOWRANK_RANKS = (8, 16, 32, 64)
 _DROPOUT_STATE = {}  # device -> int64 [2] (seed, offset) read by the mask of cd360_lowrank_add_bf16 / cd360_dropout_apply_bf16

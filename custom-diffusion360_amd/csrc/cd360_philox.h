@@ -15,6 +15,11 @@ constexpr uint32_t CD360_NOISE_STEP = 0u;       // inside a sampling step (inclu
 constexpr uint32_t CD360_NOISE_START = 1u;      // the start of a trajectory (cd360_start_noise_f32)
 constexpr uint32_t CD360_NOISE_POSTERIOR = 2u;  // DiagonalGaussianDistribution.sample (cd360_posterior_sample_f32)
 constexpr uint32_t CD360_NOISE_EDIT = 3u;       // the known region of a masked step (csrc_edit/mask_blend.hip, include/edit/cd360_edit.h)
+// a training step (csrc_train/train_stage.hip, include/train/cd360_train.h)
+constexpr uint32_t CD360_NOISE_TRAIN_SIGMA = 4u;   // the per-sample draws: sigma indices, offset noise
+constexpr uint32_t CD360_NOISE_TRAIN_TARGET = 5u;  // the noise added to the target latent
+constexpr uint32_t CD360_NOISE_TRAIN_REF_A = 6u;   // the reference views, noised by the loss
+constexpr uint32_t CD360_NOISE_TRAIN_REF_B = 7u;   // the reference views, noised again by the denoiser
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t r[4]) {
 #pragma unroll

@@ -79,6 +79,14 @@ class StandardDiffusionLossImgRef(nn.Module):
             loss_l2 = (loss * mask).sum([1, 2, 3]) / (mask.sum([1, 2, 3]) + 1e-6)
         else:
             loss_l2 = torch.mean(loss.reshape(target.shape[0], -1), 1)
+        return (loss_l2,) + self.render_terms(fg_mask_list, predicted_rgb_list, target_rgb, mask, opacity, alphas_list)
+
+    def render_terms(self, fg_mask_list, predicted_rgb_list, target_rgb, mask, opacity, alphas_list):
+        """The fg / bg / rgb terms of get_loss (:188-207) -> (loss_fg, loss_bg, loss_rgb), each [b, blocks] or an empty list: what is left of
+        get_loss when the l2 term comes from elsewhere (cd360.finetune.train_step_latents: NoiseStage.l2).  All terms in fp32."""
+        f32 = lambda t: None if t is None else t.float()
+        target_rgb, mask, opacity = map(f32, (target_rgb, mask, opacity))
+        loss_rgb, loss_fg, loss_bg = [], [], []
         n_blk = len(fg_mask_list)
         if (n_blk > 0 and n_blk == len(alphas_list) and len(predicted_rgb_list) in (0, n_blk) and (mask is not None or not predicted_rgb_list)
                 and all(fg_mask.size(1) == rgb.size(1) for fg_mask, rgb in zip(fg_mask_list, predicted_rgb_list))
@@ -102,7 +110,7 @@ class StandardDiffusionLossImgRef(nn.Module):
                     (mask_, want), rgb = resized[size], predicted_rgb_list[i]
                 terms.append(ops.render_loss(fg_mask, alphas, rgb, op, bg_w, mask_, want, mask_den))
             terms = torch.stack(terms, 1)  # [b, blocks, 3]
-            return loss_l2, terms[..., 0], terms[..., 1], (terms[..., 2] if predicted_rgb_list else loss_rgb)
+            return terms[..., 0], terms[..., 1], (terms[..., 2] if predicted_rgb_list else loss_rgb)
         if len(fg_mask_list) > 0 and len(alphas_list) > 0:
             bg_w = None  # (1 - opacity) * [opacity < 0.1] of the current map: constant until the next resize (the factor [..] is 0 / 1, so
             for fg_mask, alphas in zip(fg_mask_list, alphas_list):  # folding it into the weight first changes no bit of the product)
@@ -132,4 +140,4 @@ class StandardDiffusionLossImgRef(nn.Module):
                 err = (want - rgb.float().reshape(-1, size, size, 3).permute(0, 3, 1, 2)) ** 2
                 loss_rgb.append((err * mask_).sum([1, 2, 3]) / mask_den)
             loss_rgb = torch.stack(loss_rgb, 1)
-        return loss_l2, loss_fg, loss_bg, loss_rgb
+        return loss_fg, loss_bg, loss_rgb
