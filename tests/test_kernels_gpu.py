@@ -298,7 +298,10 @@ def test_volrender(dtype):
 
 @pytest.mark.parametrize("C", [64, 520, 640, 1280, 2048])
 def test_rowdot4(C):
-    """decoder head (nerfsd_pytorch3d.py:49-51,160): every number of 512-channel chunks a lane can own, a ragged last chunk"""
+    """decoder head (nerfsd_pytorch3d.py:49-51,160): every number of 512-channel chunks a lane can own, a ragged last chunk, on randn data
+    against the fp32 product.  111 rows are fewer than the 3072 waves a launch has at the most: every wave owns ONE row, so the row loop
+    and its prefetch hand-over (vn -> v) do not run here.  tests/test_thin_exact_gpu.py::test_rowdot_bit_equal holds the multi-row
+    launches (3072, 3073 and 6149 rows) and the exact-integer cases, bit for bit against float64."""
     from cd360 import ops
     g = torch.Generator().manual_seed(9)
     h, w = bf(torch.randn(3, 37, C, generator=g)), torch.randn(4, C, generator=g)
@@ -588,7 +591,9 @@ def test_pose_embed_c_abi():
 
 @pytest.mark.parametrize("C", [64, 640, 1280])
 def test_rowdot1(C):
-    """cd360_rowdot1_bf16 (lv = xref . vf of the reference tables, cd360/nerf.py reference_tables) vs the fp32 product"""
+    """cd360_rowdot1_bf16 (lv = xref . vf of the reference tables, cd360/nerf.py reference_tables) vs the fp32 product on randn data, one to
+    three 512-channel chunks.  3000 rows stay below the 3072 waves of a launch: one row per wave, no second trip of the row loop.
+    tests/test_thin_exact_gpu.py::test_rowdot_bit_equal holds the multi-row launches and the exact-integer cases."""
     from cd360 import ops
     torch.manual_seed(3)
     h = torch.randn(3, 1000, C).to(torch.bfloat16).float()
