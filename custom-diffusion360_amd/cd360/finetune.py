@@ -712,6 +712,16 @@ def encode_batch(first_stage, x, x_ref, seed: int, step: int, streams=None):
     return x0, z.reshape(B, n, *z.shape[1:])
 
 
+def encode_pictures(first_stage, front, pictures, masks, boxes, n_ref: int, seed: int, step: int, streams=None):
+    """From decoded frames to clean latents: cd360.pictures.PictureFront.batch (crop, resize, masks: the loader's per-picture arithmetic, on
+    the device) and then encode_batch -> (x0, x_ref, batch).  pictures / masks: uint8 device frames [H, W, 3] / [H, W], sample by sample
+    with the target first and its n_ref views behind it; boxes: front.boxes(...).  batch["jpg"] is also the loss's target_rgb,
+    batch["mask"], batch["depth"] and batch["mask_ref"] are train_step_latents' mask, opacity and mask_ref."""
+    batch = front.batch(pictures, masks, boxes, n_ref)
+    x0, x_ref = encode_batch(first_stage, batch["jpg"], batch["jpg_ref"] if n_ref else None, seed, step, streams=streams)
+    return x0, x_ref, batch
+
+
 def train_step_latents(unet: torch.nn.Module, loss_fn, optimizer, stage: NoiseStage, *, x0, x_ref, context, y, pose, target_rgb, mask, opacity,
                        drop_im=None, mask_ref=None, as_tensors: bool = False, **loss_kw):
     """One step of the fine-tuning loop from CLEAN latents: stage (sigma draws, noising, scaling: NoiseStage) -> UNet -> the l2 term

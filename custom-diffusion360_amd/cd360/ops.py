@@ -2081,6 +2081,93 @@ def train_l2_bwd(eps, x_t, x0, rows, mask, den, g) -> torch.Tensor:
     return d_eps
 
 
+# ----------------------------------------------------------------------------------------------- pictures in (include/picture/cd360_picture.h)
+# libcd360_picture.so through cd360/_picture.py.  Refusals as above: ValueError before the device check and before the library is loaded.
+PICTURE_MAX_TAPS = 64  # CD360_PICTURE_MAX_TAPS
+PICTURE_MAX_DILATE = 31  # CD360_PICTURE_MAX_DILATE
+
+
+def _window_arg(window):
+    _refuse(len(window) != 4, f"window: (left, top, w, h) is needed, got {tuple(window)}")
+    left, top, w, h = (int(v) for v in window)
+    _refuse(w <= 0 or h <= 0, f"window: an empty crop, w = {w}, h = {h}")
+    _refuse(max(abs(left), abs(top), w, h) > 1 << 30, f"window {(left, top, w, h)}: a coordinate beyond 2^30")
+    return left, top, w, h
+
+
+def _u8_picture(src: torch.Tensor, name: str, channels) -> int:
+    _refuse(not isinstance(src, torch.Tensor) or src.dtype != torch.uint8 or src.ndim not in (2, 3),
+            f"{name}: a uint8 [H, W] or [H, W, C] tensor is needed, got {getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}")
+    C = 1 if src.ndim == 2 else src.shape[2]
+    _refuse(C not in channels, f"{name}: {C} channels, served: {tuple(channels)}")
+    H, W = src.shape[:2]
+    _refuse(H <= 0 or W <= 0, f"{name} is empty: {tuple(src.shape)}")
+    _refuse(src.stride(1) != C or (src.ndim == 3 and C > 1 and src.stride(2) != 1) or src.stride(0) < W * C,
+            f"{name}: pixels of {C} neighbouring bytes in rows at least {W * C} bytes apart are needed, got strides {tuple(src.stride())}")
+    _refuse(H * src.stride(0) >= 1 << 31, f"{name}: {H} rows of {src.stride(0)} bytes do not fit 32-bit offsets")
+    return C
+
+
+def _tap_table(tab, n_out: int, name: str) -> int:
+    _refuse(not isinstance(tab, (tuple, list)) or len(tab) != 3, f"{name}: (xmin int32 [n], size int32 [n], weights fp32 [n, T]) is needed")
+    lo, size, wt = tab
+    _refuse(any(not isinstance(t, torch.Tensor) or not t.is_contiguous() for t in tab) or lo.dtype != torch.int32 or size.dtype != torch.int32
+            or wt.dtype != torch.float32 or wt.ndim != 2 or tuple(lo.shape) != (n_out,) or tuple(size.shape) != (n_out,) or wt.shape[0] != n_out,
+            f"{name}: contiguous int32 [{n_out}], int32 [{n_out}] and fp32 [{n_out}, T] are needed")
+    T = wt.shape[1]
+    _refuse(not 1 <= T <= PICTURE_MAX_TAPS, f"{name}: rows of {T} taps, served: 1..{PICTURE_MAX_TAPS} (CD360_PICTURE_MAX_TAPS)")
+    return T
+
+
+def picture_resample(src: torch.Tensor, window, xtab, ytab, oh: int, ow: int, fill: int = 0, round_u8: bool = True, div: float = 255.0,
+                     mul: float = 2.0, add: float = -1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Crop + separable resize of one uint8 picture into fp32 planes [C, oh, ow] (cd360_picture_resample_u8): src uint8 [H, W, C] (C = 1 or
+    3; [H, W] is one channel) with any row stride; window = (left, top, w, h) in picture pixels, which may leave the picture (`fill`
+    there); xtab / ytab = (xmin, size, weights) device tensors resizing w -> ow and h -> oh (cd360.pictures.device_taps).  Horizontal
+    pass, then vertical, the taps in rising order in fp32; round_u8: round and clamp to 0..255 after each pass (the image library's uint8
+    storage); last (v / div) * mul + add.  out: a contiguous fp32 [C, oh, ow] view to write, e.g. one slot of a batch tensor."""
+    from . import _picture
+    C = _u8_picture(src, "src", (1, 3))
+    H, W = src.shape[:2]
+    left, top, w, h = _window_arg(window)
+    _refuse(oh <= 0 or ow <= 0, f"oh, ow must be positive, got {oh}, {ow}")
+    tx, ty = _tap_table(xtab, ow, "xtab"), _tap_table(ytab, oh, "ytab")
+    _refuse(not 0 <= int(fill) <= 255, f"fill = {fill}: a byte is needed")
+    _refuse(not all(math.isfinite(float(v)) for v in (div, mul, add)) or float(div) == 0.0, f"div, mul, add = {div}, {mul}, {add}: finite values, div != 0")
+    _refuse(C * h * ow >= 1 << 31 or C * oh * ow >= 1 << 31, f"{C} planes of {h} x {ow} or {oh} x {ow} do not fit 32-bit offsets")
+    out = _out_arg(out, (C, oh, ow), torch.float32, src, "src")
+    _need_gpu(src, *xtab, *ytab, out)
+    work = torch.empty((C, h, ow), dtype=torch.float32, device=src.device)
+    check(_picture.load().cd360_picture_resample_u8(_ptr(src), H, W, C, src.stride(0), left, top, w, h, int(fill), _ptr(xtab[0]), _ptr(xtab[1]),
+                                                    _ptr(xtab[2]), tx, _ptr(ytab[0]), _ptr(ytab[1]), _ptr(ytab[2]), ty, oh, ow, int(bool(round_u8)),
+                                                    float(div), float(mul), float(add), _ptr(work), _ptr(out), _stream()),
+          "cd360_picture_resample_u8")
+    return out
+
+
+def picture_mask(src: torch.Tensor, window, oh: int, ow: int, thr: int = 125, k: int = 7, want=(True, True, True), out=None):
+    """The maps of one uint8 mask [H, W] (cd360_picture_mask_u8) -> (opacity, mask, inside), fp32 [oh, ow] each, None where `want` says so:
+    opacity = (src > thr) through the crop `window` (0 outside the picture) and the nearest resize of a boolean image; mask = its k x k
+    dilation with zero padding, clamp(conv2d(opacity, ones), 0, 1); inside = the all-ones picture through the same crop and resize.  out:
+    three contiguous fp32 [oh, ow] views (or None) to write instead of fresh tensors."""
+    from . import _picture
+    _u8_picture(src, "src", (1,))
+    H, W = src.shape[:2]
+    left, top, w, h = _window_arg(window)
+    _refuse(oh <= 0 or ow <= 0 or oh * ow >= 1 << 31, f"oh, ow must be positive with oh * ow < 2^31, got {oh}, {ow}")
+    _refuse(not 0 <= int(thr) <= 255, f"thr = {thr}: a byte is needed")
+    _refuse(k < 1 or k % 2 == 0 or k > PICTURE_MAX_DILATE, f"k = {k}: an odd window of 1..{PICTURE_MAX_DILATE} is needed")
+    out = (None, None, None) if out is None else tuple(out)
+    _refuse(len(want) != 3 or len(out) != 3 or not any(want), "want, out: three entries (opacity, mask, inside), one wanted at the least")
+    outs = [_out_arg(o, (oh, ow), torch.float32, src, "src") if wanted else None for o, wanted in zip(out, want)]
+    live = [o for o in outs if o is not None]
+    _refuse(any(_overlaps(a, b) for n, a in enumerate(live) for b in live[n + 1:]), "out: two outputs overlap")
+    _need_gpu(src, *live)
+    check(_picture.load().cd360_picture_mask_u8(_ptr(src), H, W, src.stride(0), int(thr), left, top, w, h, oh, ow, k, _ptr(outs[0]), _ptr(outs[1]),
+                                                _ptr(outs[2]), _stream()), "cd360_picture_mask_u8")
+    return tuple(outs)
+
+
 # ----------------------------------------------------------------------------------------------- rank-r adapters (add_lora=True)
 LOWRANK_RANKS = (8, 16, 32, 64)
 _DROPOUT_STATE = {}  # device -> int64 [2] (seed, offset) read by the mask of cd360_lowrank_add_bf16 / cd360_dropout_apply_bf16
