@@ -163,6 +163,15 @@ def near_midpoint(x, err):
     return ((y - torch.floor(y) - 0.5).abs() * u <= err) & (x != 0), u
 
 
+def midpoints_within(x, err):
+    """(count, ulp): how many bf16 rounding midpoints lie within err (absolute) of |x|, counted at the spacing of x's own binade -- for an err
+    below half a spacing this is near_midpoint's flag."""
+    y, u = grid(x)
+    y, e = y.abs(), err / u
+    n = torch.floor(y + e - 0.5) - torch.ceil(y - e - 0.5) + 1
+    return n.clamp_min(0) * (x != 0), u
+
+
 def tau(sa_c, x):
     return math.log(2.0) * (C_QK * sa_c + C_X * x.abs()) + C_E
 
@@ -261,9 +270,10 @@ def _lse(m2, l, f32):
     return R(R(m2 + (torch.log2(l.float()).double() if f32 else torch.log2(l)), f32) * float(LN2_F32), f32)
 
 
-def _tiled(s_all, sa_c, v, c, tile, fault=None, f32=False, order=0, clean=None) -> Fwd:
+def _tiled(s_all, sa_c, v, c, tile, fault=None, f32=False, order=0, clean=None, tau_extra=None) -> Fwd:
     """The eager pipeline over the keys given: s_all raw scores [B, H, Nq, n], x = fma(s, c, -m c).  tile >= n: the whole-row pipeline.
-    clean: the fault-free run of the same call (p_norm, p_alpha read their scales from it)."""
+    clean: the fault-free run of the same call (p_norm, p_alpha read their scales from it).  tau_extra [B, H, Nq, n]: a relative
+    uncertainty of p from outside the pipeline (a q that may round either way, tests/qproj_cases.py), added to tau."""
     n = s_all.shape[-1]
     shape = s_all.shape[:-1]
     m = s_all.new_full(shape, float("-inf"))
@@ -290,9 +300,11 @@ def _tiled(s_all, sa_c, v, c, tile, fault=None, f32=False, order=0, clean=None) 
         ps.append(p)
         if not f32:
             tp = tau(sa, x)
+            if tau_extra is not None:    # (may exceed a spacing of p: every midpoint it reaches counts)
+                tp = tp + tau_extra[..., t * tile:(t + 1) * tile]
             taus.append(tp)
-            flag, u = near_midpoint(p, tp * p)
-            nflag += int(flag.sum())
+            flag, u = near_midpoint(p, tp * p) if tau_extra is None else midpoints_within(p, tp * p)
+            nflag += int((flag > 0).sum())
             F = F * alpha[..., None] + torch.matmul(flag * u, vt.abs())
         m = m_new
         ms.append(m)
@@ -305,11 +317,11 @@ def scores(q, k, f32=False, order=0):
     return mm(q, k.transpose(-1, -2), f32, order), torch.matmul(q.abs(), k.abs().transpose(-1, -2))
 
 
-def emulate_row(case: Case, fault=None, f32=False, order=0) -> Fwd:
+def emulate_row(case: Case, fault=None, f32=False, order=0, tau_extra=None) -> Fwd:
     """attn_smallk_kernel<NKB, false> / the <= 96-key epilogue of the fused q projection."""
     s, sa = scores(case.q, case.k, f32, order)
     clean = _tiled(s, sa * C, case.v, C, 1 << 30) if fault in ("p_norm", "p_alpha") else None
-    return _tiled(s, sa * C, case.v, C, 1 << 30, fault, f32, order, clean)
+    return _tiled(s, sa * C, case.v, C, 1 << 30, fault, f32, order, clean, tau_extra)
 
 
 def emulate_eager(case: Case, fault=None, f32=False, order=0) -> Fwd:
